@@ -8,7 +8,12 @@ tick in between and episodes restarting as they end).  N GPUs: one process per G
 own 65,536 envs (weak scaling, no collective on the data path; the reference's parallelism is an
 embarrassingly parallel seed sweep, hyperparam_tuning.py:85-91).
 
-Usage: python bench.py [--gpus N --steps K --warmup W].  N > 1 runs one rank per GPU: under
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full].  A plain run sets up,
+warms up, times the K steps and prints the line; ``--dump-outputs DIR`` also writes what the last timed step left
+(a fixed sample of the envs' Q-tables, key sets and env states, ``DIR/<name>.npy``).  ``--full`` adds everything
+else the line can carry: the parity check against the host build, the sustained rate, the two CPU baselines with
+the oracle parity, and on N > 1 ranks the partitioned leg (with --partition: the parity check and the env-sharded
+comparison).  N > 1 runs one rank per GPU: under
 torch.distributed.run (the driver's launch) every rank checks WORLD_SIZE == N and that N devices are
 visible; started without it, bench.py launches ``torch.distributed.run --nproc-per-node N`` itself as a
 child process (before any HIP call) and exits with its return code.
@@ -422,6 +427,39 @@ def parity_field(dist, n_checked: int, bad, device=None, threads: int = 0):
             "parity_first_mismatches": list(bad[:4])}
 
 
+DUMP_ENVS = 32  # envs of the --dump-outputs sample (fewer where 32 Q-tables exceed DUMP_BYTES)
+DUMP_BYTES = 56 << 20  # of Q-tables; with the key sets and env states the files stay under 64 MB
+
+
+def dump_outputs(b, out_dir: str, last_step):
+    """--dump-outputs: what the timed path left after its last step, as float64 ``<name>.npy`` files -- of a fixed
+    spread sample of this batch's envs (parity.spread: the same envs for the same arguments) the compact Q-table,
+    the key-set bitmap words and the env state (clock and phase, semaphore records as their low and high 32 bits,
+    train cells and bits), and the last step's own results (decisions returned, the launch's decisions and ticks,
+    the batch's decisions so far).  Everything is bit-exact from run to run, so two builds compare file by file."""
+    parity = importlib.import_module(PKG + ".parity")
+    n = max(1, min(DUMP_ENVS, DUMP_BYTES // (8 * int(b.cm.q_per_env))))
+    pick = parity.spread(b.E, n)
+    q, keys, clock, sem, cells, bits = [], [], [], [], [], []
+    for e in pick:
+        qe, te = b.q_raw(e)
+        el, ph, se, pos, bt = parity.env_state(b, e)
+        q.append(qe)
+        keys.append(te)
+        clock.append([el, ph])
+        sem.append(np.stack([se & np.uint64(0xFFFFFFFF), se >> np.uint64(32)], axis=-1))
+        cells.append(pos)
+        bits.append(bt)
+    cnt = b.counters()
+    arrays = {"envs": pick, "q": q, "key_set": keys, "env_clock": clock, "semaphores": sem, "train_cells": cells,
+              "train_bits": bits,
+              "last_step": [last_step, cnt["last_launch_decisions"], cnt["last_launch_ticks"], cnt["decisions"]]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -430,13 +468,21 @@ def main():
     ap.add_argument("--decisions", type=int, default=1024, help="agent-env-steps per env per step (one launch)")
     ap.add_argument("--envs", type=int, default=65536, help="envs per GPU")
     ap.add_argument("--config", default="c3")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left (a fixed sample of the envs' Q-tables, "
+                         "key sets and env states) as DIR/<name>.npy, float64, under 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: the parity check against the host build, the "
+                         "sustained rate, the CPU baselines with the oracle parity, the partitioned leg of N > 1 ranks "
+                         "(--partition: the parity check and the env-sharded comparison)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: seconds of the CPU baselines")
     ap.add_argument("--sustain-seconds", type=float, default=8.0,
-                    help="after the parity check, repeat the step for about this long and report the rate as "
+                    help="--full: after the parity check, repeat the step for about this long and report the rate as "
                          "'sustained' (0: skip)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--verify-envs", type=int, default=32,
-                    help="envs per rank re-run on the host build after timing and compared bit-exactly (0: none)")
+                    help="--full: envs per rank re-run on the host build after timing and compared bit-exactly "
+                         "(0: none)")
     ap.add_argument("--experimental", action="store_true",
                     help="accept a tuning / experiment build as SFL_LIB (its defines are reported; SFL_X_* / SFL_AB_* "
                          "builds compute wrong results)")
@@ -462,6 +508,10 @@ def main():
                     help="TEST ONLY: run the ranks on the host build of the kernel body (libsfl_hostsim.so, gloo) to "
                          "rehearse the launcher without a GPU; the line says so and is no measurement")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    if args.dump_outputs and args.partition:
+        ap.error("--dump-outputs writes the env-sharded bench's outputs; --partition has none to write")
     rc = launch_or_check(args, sys.argv[1:])
     if rc is not None:
         sys.exit(rc)
@@ -476,7 +526,8 @@ def main():
     par = importlib.import_module(PKG + ".parallel")
     world, rank, local = par.world()
     pool = None
-    if world == 1 and not args.no_cpu and not host and not any(k.startswith("ROCPROF") for k in os.environ):
+    cpu_legs = args.full and world == 1 and not args.no_cpu and not host
+    if cpu_legs and not any(k.startswith("ROCPROF") for k in os.environ):
         # (before the first HIP call; never under rocprofv3, whose preload initialises the GPU at start)
         pool = start_oracle_pool(oracle_cores())
     dist, dev, red_dev = dist_setup(par, local, host)
@@ -531,9 +582,12 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     dt, total_all = par.reduce_timing(dist, dt, float(total), device=red_dev)
-    # after the timed region: a spread sample of every rank's envs re-run on the host build, bit-exact
-    checked, bad, vthreads = 0, ["not verified (--verify-envs 0)"], 0
-    if args.verify_envs > 0:
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (before anything else advances the envs)
+        dumped = dump_outputs(b, args.dump_outputs, n)
+    # --full, after the timed region: a spread sample of every rank's envs re-run on the host build, bit-exact
+    checked, bad, vthreads = 0, ["not verified (--verify-envs 0)" if args.full else "not verified (a --full run is)"], 0
+    if args.full and args.verify_envs > 0:
         checked, bad, vthreads = verify_fused(b, cm, seeds, [args.decisions] * (args.warmup + args.steps),
                                               args.verify_envs)
     pfield = parity_field(dist, checked, bad, device=red_dev, threads=vthreads)
@@ -541,7 +595,7 @@ def main():
     # synchronize on both sides, max over ranks) -- the rate over a longer window than the K timed steps, so that
     # a sampler of the GPU's activity around the run sees the kernel running
     sustained = None
-    if args.sustain_seconds > 0 and not host and args.steps > 0:
+    if args.full and args.sustain_seconds > 0 and not host:
         n_sus = max(1, int(math.ceil(args.sustain_seconds / max(1e-6, dt / args.steps))))
         barrier()
         t1 = time.perf_counter()
@@ -591,12 +645,15 @@ def main():
             "devices": devices,
             **pfield,
             "sustained": sustained,
+            "full": bool(args.full),
         }
+        if dumped is not None:
+            res["dumped_outputs"] = dumped
         if host:
             res["rehearsal"] = ("--rehearse-on-host: every rank ran the host build of the kernel body; a launcher "
                                 "rehearsal, not a GPU measurement")
             res["roofline"] = None
-        if world == 1 and not args.no_cpu and not host:
+        if cpu_legs:
             res["cpu_baseline"] = cpu_baseline(cm, args.cpu_seconds, args.config)
             try:
                 res["cpu_oracle_baseline"] = cpu_oracle_baseline(args.config, args.cpu_seconds / 2, pool=pool,
@@ -612,7 +669,7 @@ def main():
         if not printed:
             printed.append(1)
             print(json.dumps(r), file=JSON_OUT[0], flush=True)
-    if world > 1 and os.environ.get("SFL_NO_PARTITION_LEG") != "1":
+    if args.full and world > 1 and os.environ.get("SFL_NO_PARTITION_LEG") != "1":
         leg = partition_leg(par, dist, world, rank, dev, red_dev, devices, res, emit, host=host)
         if rank == 0:
             res["partition_leg"] = leg
@@ -689,7 +746,7 @@ def partition_run(args, par, dist, world, rank, dev, red_dev, devices, host: boo
     # the break-even comparison: the same envs run env-sharded on the fused kernel -- every rank its
     # own envs with all their Q rows, no exchange -- timed the same way, before the partitioned job allocates
     fused = None
-    if getattr(args, "compare_fused", True):
+    if args.full and getattr(args, "compare_fused", True):
         runtime = importlib.import_module(PKG + ".runtime")
         fb = runtime.Batch(cm, HP, seeds, device=dev, lib=lib)
         fb.learn_begin()
@@ -741,8 +798,8 @@ def partition_run(args, par, dist, world, rank, dev, red_dev, devices, host: boo
     dt, total_all = par.reduce_timing(dist, dt, total, device=red_dev)
     # after the timed region: a spread sample of the job's envs, this rank's owned rows of them and the
     # state of those it simulates, vs a fused single-process host run of their seeds
-    checked, bad, vthreads = 0, ["not verified (--verify-envs 0)"], 0
-    if args.verify_envs > 0:
+    checked, bad, vthreads = 0, ["not verified (--verify-envs 0)" if args.full else "not verified (a --full run is)"], 0
+    if args.full and args.verify_envs > 0:
         parity = importlib.import_module(PKG + ".parity")
         hlib, vthreads = host_verifier()
         pick = parity.spread(world * E, args.verify_envs)
@@ -808,7 +865,7 @@ def partition_run(args, par, dist, world, rank, dev, red_dev, devices, host: boo
     return res
 
 
-# configs[4] inside every N > 1 run of the default bench: the driver launches bench.py itself under
+# configs[4] inside every N > 1 --full run of the default bench: such a run goes through
 # torch.distributed.run, so this is where the partitioned exchange meets RCCL on a multi-GPU node.  A short run
 # (c5, 2,048 envs per GPU, 4 timed steps of 256 decisions after 2 warm-up steps, 8 envs of the job re-run on
 # the host build), after the env-sharded measurement, parity-checked like
@@ -820,7 +877,7 @@ def partition_run(args, par, dist, world, rank, dev, red_dev, devices, host: boo
 # (one cohort: the leg is the first contact of the exchange with RCCL, so it runs the single-job path with one
 # communicator; --partition --cohorts N measures the cohort pipeline)
 PARTITION_LEG = dict(config="c5", envs=2048, decisions=256, steps=4, warmup=2, verify_envs=8, remote_rows=False,
-                     virtual_ranks=0, cohorts=1)
+                     virtual_ranks=0, cohorts=1, full=True)
 PARTITION_LEG_HOST = dict(PARTITION_LEG, envs=4, decisions=24, steps=1)
 PARTITION_LEG_TIMEOUT_S = 300.0
 PARTITION_LEG_FAILED = 3

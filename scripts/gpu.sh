@@ -6,7 +6,7 @@
 # Steps:
 #   tests      pytest -m gpu (PYTEST_K: a -k filter)
 #   smoke      __graft_entry__.smoke()
-#   bench      the default bench line (CPU baselines, oracle parity); BENCH_ARGS appended
+#   bench      the --full bench line (parity check, sustained rate, CPU baselines, oracle parity); BENCH_ARGS appended
 #   driver     the driver's own command: bench.py --steps 20 --warmup 5
 #   ktrace     rocprofv3 --kernel-trace --stats of a short bench (BENCH_ARGS)
 #   pmc        the HBM-traffic passes (FETCH_SIZE, WRITE_SIZE, L2 hit/miss, memory-side requests) of a short bench
@@ -55,7 +55,7 @@ for S in "$@"; do
     smoke)
       timeout -k 10 300 python __graft_entry__.py > $OUT/smoke.log 2>&1; rc=$?; tail -1 $OUT/smoke.log; ok $rc "smoke" ;;
     bench)
-      timeout -k 10 600 python bench.py ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err; rc=$?
+      timeout -k 10 600 python bench.py --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err; rc=$?
       [ $rc -eq 0 ] || tail -5 $OUT/bench.err; ok $rc "bench"; line $OUT/bench.json ;;
     driver)
       timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $OUT/driver.json 2> $OUT/driver.err; rc=$?
@@ -74,7 +74,7 @@ for S in "$@"; do
       TAG=${TAG:-gpu} bash scripts/gpu_waitsplit.sh > $OUT/waitsplit.log; ok $? "waitsplit"
       python scripts/pmc_summary.py $OUT profiles/${P}_pmc.json $OUT/prof.json > $OUT/pmc_summary.log; ok $? "pmc summary"
       cp profiles/${P}_pmc.json $OUT/
-      timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; rc=$?
+      timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; rc=$?
       [ $rc -eq 0 ] || tail -5 $OUT/bench.err; ok $rc "bench"; line $OUT/bench.json
       timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $OUT/driver.json 2> $OUT/driver.err; rc=$?
       [ $rc -eq 0 ] || tail -5 $OUT/driver.err; ok $rc "driver"; line $OUT/driver.json ;;
@@ -86,7 +86,7 @@ for S in "$@"; do
       TAG=${TAG:-gpu}/c2 BENCH_ARGS="$B --verify-envs 0" DEC=$((4096*1024)) bash scripts/gpu_waitsplit.sh > $OUT/c2_waitsplit.log; ok $? "c2 waitsplit"
       python scripts/pmc_summary.py $OUT/c2 profiles/${P}_c2_4096_pmc.json $OUT/c2_prof.json > $OUT/c2_pmc_summary.log; ok $? "c2 pmc summary"
       cp profiles/${P}_c2_4096_pmc.json $OUT/
-      timeout -k 10 300 python bench.py $B --steps 10 --warmup 2 --no-cpu > $OUT/c2_bench.json 2> $OUT/c2_bench.err; ok $? "c2 bench"
+      timeout -k 10 300 python bench.py --full $B --steps 10 --warmup 2 --no-cpu > $OUT/c2_bench.json 2> $OUT/c2_bench.err; ok $? "c2 bench"
       line $OUT/c2_bench.json ;;
     c2dec)  # configs[1] at longer launches (decisions per env per step): does the one-generation tail amortise?
       for D in ${C2DEC:-1024 4096 16384}; do
@@ -94,18 +94,18 @@ for S in "$@"; do
         line $OUT/c2_dec$D.json
       done ;;
     c2big)
-      timeout -k 10 300 python bench.py --config c2 --steps 10 --warmup 2 --no-cpu > $OUT/c2_65536_bench.json 2> $OUT/c2_65536.err; ok $? "c2 65536"
+      timeout -k 10 300 python bench.py --full --config c2 --steps 10 --warmup 2 --no-cpu > $OUT/c2_65536_bench.json 2> $OUT/c2_65536.err; ok $? "c2 65536"
       line $OUT/c2_65536_bench.json ;;
     c5fused)
-      timeout -k 10 300 python bench.py --config c5 --envs 16384 --steps 4 --warmup 1 --no-cpu > $OUT/c5_fused_bench.json 2> $OUT/c5_fused.err; ok $? "c5 fused"
+      timeout -k 10 300 python bench.py --full --config c5 --envs 16384 --steps 4 --warmup 1 --no-cpu > $OUT/c5_fused_bench.json 2> $OUT/c5_fused.err; ok $? "c5 fused"
       line $OUT/c5_fused_bench.json ;;
     part)
-      timeout -k 10 400 python bench.py --partition --steps 3 --warmup 1 --decisions 1024 --virtual-ranks 8 --verify-envs 4 ${PART_ARGS} > $OUT/part.json 2> $OUT/part.err; rc=$?
+      timeout -k 10 400 python bench.py --full --partition --steps 3 --warmup 1 --decisions 1024 --virtual-ranks 8 --verify-envs 4 ${PART_ARGS} > $OUT/part.json 2> $OUT/part.err; rc=$?
       [ $rc -eq 0 ] || tail -5 $OUT/part.err; ok $rc "part"
       line $OUT/part.json
       python -c "import json;d=json.load(open('$OUT/part.json'));print('  fused env-sharded %.1fM/s, vs_env_sharded_fused %.3f' % (d['env_sharded_fused']['value']/1e6, d['vs_env_sharded_fused']))" ;;
     partrccl)  # the partition rehearsal with its segments as RCCL collectives of a one-rank group (RCCL's round cost)
-      timeout -k 10 400 python bench.py --partition --steps 3 --warmup 1 --decisions 1024 --virtual-ranks 8 --verify-envs 4 --rccl-one-rank ${PART_ARGS} > $OUT/part_rccl.json 2> $OUT/part_rccl.err; rc=$?
+      timeout -k 10 400 python bench.py --full --partition --steps 3 --warmup 1 --decisions 1024 --virtual-ranks 8 --verify-envs 4 --rccl-one-rank ${PART_ARGS} > $OUT/part_rccl.json 2> $OUT/part_rccl.err; rc=$?
       [ $rc -eq 0 ] || tail -5 $OUT/part_rccl.err; ok $rc "part rccl"
       line $OUT/part_rccl.json
       python -c "import json;d=json.load(open('$OUT/part_rccl.json'));c=d['config'];print('  exchange %s, %s collectives/round, %.1f rounds/step, cohorts %s' % (c['exchange'], c['collectives_per_round'], c['rounds_per_step'], c['cohorts']))" ;;
@@ -115,13 +115,13 @@ for S in "$@"; do
         i=$((i+1))
         export SFL_LIB=$GRAFT_REPO_ROOT/network-distributed-q-learning_amd/$L.so
         V="--verify-envs ${VERIFY_ENVS:-0} --experimental"; [ "$L" = "libsfl" ] && V=""
-        timeout -k 10 300 python bench.py --steps ${STEPS:-10} --warmup 2 --no-cpu --sustain-seconds 0 $V ${BENCH_ARGS} > $OUT/ab_${i}_${L}.json 2> $OUT/ab_${i}_${L}.err; ok $? "ab $L"
+        timeout -k 10 300 python bench.py --full --steps ${STEPS:-10} --warmup 2 --no-cpu --sustain-seconds 0 $V ${BENCH_ARGS} > $OUT/ab_${i}_${L}.json 2> $OUT/ab_${i}_${L}.err; ok $? "ab $L"
         line $OUT/ab_${i}_${L}.json
       done
       unset SFL_LIB ;;
     rehearse)  # the N > 1 bench path on this one GPU: REH_N gloo ranks sharing device 0 (not the RCCL transport)
       for N in ${REH_N:-2 4}; do
-        SFL_DIST_BACKEND=gloo SFL_DEVICE=0 timeout -k 10 600 python bench.py --gpus $N --envs 8192 --steps 3 --warmup 1 > $OUT/gpus$N.json 2> $OUT/gpus$N.err; rc=$?
+        SFL_DIST_BACKEND=gloo SFL_DEVICE=0 timeout -k 10 600 python bench.py --full --gpus $N --envs 8192 --steps 3 --warmup 1 > $OUT/gpus$N.json 2> $OUT/gpus$N.err; rc=$?
         [ $rc -eq 0 ] || tail -5 $OUT/gpus$N.err; ok $rc "rehearse --gpus $N"
         python -c "import json;d=json.loads([l for l in open('$OUT/gpus$N.json') if l.startswith('{')][0]);L=d.get('partition_leg') or {};print('  world %d %s %.1fM/s parity %s (%d envs, %d threads/rank); leg %s parity %s vs fused %s' % (d['world_size'], d['backend'], d['value']/1e6, d['parity'], d['parity_envs_checked'], d['parity_threads_per_rank'], L.get('value'), L.get('parity'), L.get('vs_env_sharded_fused')))"
       done ;;
@@ -130,7 +130,7 @@ for S in "$@"; do
       for E in ${ABENV}; do
         i=$((i+1))
         N=$(echo $E | tr '=' '_')
-        env $E timeout -k 10 300 python bench.py --steps ${STEPS:-10} --warmup 2 --no-cpu --sustain-seconds 0 ${BENCH_ARGS} > $OUT/abenv_${i}_${N}.json 2> $OUT/abenv_${i}_${N}.err; ok $? "abenv $E"
+        env $E timeout -k 10 300 python bench.py --full --steps ${STEPS:-10} --warmup 2 --no-cpu --sustain-seconds 0 ${BENCH_ARGS} > $OUT/abenv_${i}_${N}.json 2> $OUT/abenv_${i}_${N}.err; ok $? "abenv $E"
         line $OUT/abenv_${i}_${N}.json
       done ;;
     eval)  # the 15-train sweep config with malfunctions, 3 seeds x 10 evaluations, vs the host build's run

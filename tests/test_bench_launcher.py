@@ -28,7 +28,7 @@ def _bench(args, env, timeout=300):
 
 
 def test_gpus_2_launches_two_ranks_end_to_end():
-    r = _bench(["--gpus", "2", "--rehearse-on-host", "--config", "c2", "--envs", "4", "--decisions", "32",
+    r = _bench(["--gpus", "2", "--full", "--rehearse-on-host", "--config", "c2", "--envs", "4", "--decisions", "32",
                 "--steps", "2", "--warmup", "1", "--verify-envs", "2"], _env(OMP_NUM_THREADS="2"))
     assert r.returncode == 0, r.stderr[-3000:]
     assert "launching" in r.stderr and "--nproc-per-node=2" in r.stderr
@@ -54,7 +54,7 @@ def test_gpus_4_host_rehearsal_runs_the_partitioned_leg():
     exchange per round."""
     env = _env()
     env.pop("OMP_NUM_THREADS", None)  # (the ranks bound their host-build threads themselves)
-    r = _bench(["--gpus", "4", "--rehearse-on-host", "--config", "c2", "--envs", "4", "--decisions", "32",
+    r = _bench(["--gpus", "4", "--full", "--rehearse-on-host", "--config", "c2", "--envs", "4", "--decisions", "32",
                 "--steps", "2", "--warmup", "1", "--verify-envs", "2"], env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -80,9 +80,9 @@ def test_gpus_4_host_rehearsal_runs_the_partitioned_leg():
 def test_gpus_2_host_rehearsal_partition_with_cohorts():
     """bench.py --partition --cohorts 2 on two host-build ranks over gloo: each rank's envs as two cohort jobs
     (a process group each), owned rows and env states of the sampled envs checked against a fused host run."""
-    r = _bench(["--gpus", "2", "--rehearse-on-host", "--partition", "--cohorts", "2", "--config", "c5", "--envs", "4",
-                "--decisions", "24", "--steps", "1", "--warmup", "1", "--verify-envs", "4"], _env(OMP_NUM_THREADS="2"),
-               timeout=600)
+    r = _bench(["--gpus", "2", "--full", "--rehearse-on-host", "--partition", "--cohorts", "2", "--config", "c5",
+                "--envs", "4", "--decisions", "24", "--steps", "1", "--warmup", "1", "--verify-envs", "4"],
+               _env(OMP_NUM_THREADS="2"), timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout

@@ -58,14 +58,27 @@ def test_exception_on_rank0_prints_the_line_and_exits_nonzero(monkeypatch):
 
 
 def test_exception_on_another_rank_waits_for_rank0_then_exits_nonzero(monkeypatch):
-    held = []
+    import threading
+    held, timers = [], []
     monkeypatch.setattr(bench, "_hold_then_exit", lambda s: held.append(s))
+
+    class Timer(threading.Timer):
+        def __init__(self, *a, **k):
+            super().__init__(*a, **k)
+            timers.append(self)
+    monkeypatch.setattr(threading, "Timer", Timer)
 
     def boom(*a, **k):
         raise RuntimeError("RCCL error")
     monkeypatch.setattr(bench, "partition_run", boom)
     printed = []
-    bench.partition_leg(None, None, 2, 1, 0, "cuda", [0, 0], None, printed.append)
+    try:
+        bench.partition_leg(None, None, 2, 1, 0, "cuda", [0, 0], None, printed.append)
+    finally:
+        # the rank would have ended in _hold_then_exit; here its watchdog is still armed and, left alone, ends
+        # the test process with PARTITION_LEG_FAILED once the suite has run for another 330 s
+        assert len(timers) == 1
+        timers[0].cancel()
     assert not printed  # (rank 0 prints)
     # it waits past rank 0's watchdog before it ends, so the launcher does not stop rank 0 first
     assert len(held) == 1 and held[0] > bench.PARTITION_LEG_TIMEOUT_S
