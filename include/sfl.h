@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define SFL_ABI_VERSION 8
+#define SFL_ABI_VERSION 9
 
 typedef struct sfl_handle sfl_handle;
 
@@ -270,6 +270,25 @@ int sfl_env_step(sfl_handle* h, sfl_env_io* io);
  * wavefronts' total; their ratios split the launches' kernel time (switch_env.py:67-73 accumulators).
  * n >= 8. */
 int sfl_get_phase_cycles(sfl_handle* h, uint64_t* cycles, int32_t n);
+
+/* ---- hyperparameter groups: a whole epsilon / lr grid in one lock-step batch ----
+ * The reference sweeps epsilon, epsilon_decay_rate, lr and lr_decay_rate as one process per grid cell
+ * (hyperparam_tuning.py -> main.py); here the cells are envs of one handle.  Env e learns with
+ * groups[env_group[e]]: its epsilon(n) and lr(n) schedules (distr_q.py:59-79) come from that group's tables and
+ * scalars instead of the handle's sfl_hparams.  Only these four keys are per group: gamma, default_q, max_steps
+ * and ntab (the length of every group's tables) stay the handle's.  n_groups == 0 returns to the handle's own
+ * sfl_hparams.  1 <= n_groups <= 4096, every env_group[e] < n_groups.  The call copies the arrays, is
+ * synchronous and takes effect from the next launch.  Refused on a graph-partitioned handle and in
+ * external-action mode; on a grouped handle a per-decision trace (sfl_run_args.trace) is refused and the phase
+ * cycles do not advance (the grouped kernels are built plain only). */
+typedef struct {
+  double epsilon, epsilon_decay_rate, lr, lr_decay_rate;
+  const double* eps_tab;   /* [ntab of the handle] epsilon * decay**n, host arithmetic */
+  const double* lr_tab;    /* [ntab] lr * lr_decay**n */
+} sfl_hparam_group;
+#define SFL_MAX_HPARAM_GROUPS 4096
+int sfl_set_hparam_groups(sfl_handle* h, int32_t n_groups, const sfl_hparam_group* groups,
+                          const uint16_t* env_group /* [n_envs] */);
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PRODUCT_LIB = os.path.join(HERE, "libsfl.so")
-ABI_VERSION = 8  # include/sfl.h SFL_ABI_VERSION
+ABI_VERSION = 9  # include/sfl.h SFL_ABI_VERSION
 
 P = C.POINTER
 
@@ -40,6 +40,17 @@ class HParams(C.Structure):
         ("lr_decay_rate", C.c_double), ("default_q", C.c_double), ("max_steps", C.c_int64), ("ntab", C.c_int32),
         ("eps_tab", P(C.c_double)), ("lr_tab", P(C.c_double)),
     ]
+
+
+class HParamGroup(C.Structure):
+    """sfl_hparam_group: one group's epsilon / lr schedule (sfl_set_hparam_groups)."""
+    _fields_ = [
+        ("epsilon", C.c_double), ("epsilon_decay_rate", C.c_double), ("lr", C.c_double), ("lr_decay_rate", C.c_double),
+        ("eps_tab", P(C.c_double)), ("lr_tab", P(C.c_double)),
+    ]
+
+
+MAX_HPARAM_GROUPS = 4096  # include/sfl.h SFL_MAX_HPARAM_GROUPS
 
 
 class RunArgs(C.Structure):
@@ -106,6 +117,8 @@ EXPORTS = {
     "sfl_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sfl_part_set_local_rows": (C.c_int, [C.c_void_p, P(C.c_uint8)]),
     "sfl_part_get_q": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_double), P(C.c_uint32)]),
+    # hyperparameter groups (runtime.Batch hparam_groups, sweep.py)
+    "sfl_set_hparam_groups": (C.c_int, [C.c_void_p, C.c_int32, P(HParamGroup), P(C.c_uint16)]),
 }
 
 

@@ -18,11 +18,9 @@
 #include "sfl_kwave_g.h"
 #include "sfl_wave.h"
 
-SFL_KWAVE_V7(extern template)  // (defined in sfl_kwave_v7.hip)
-
-#ifndef SFL_WAVE_OCC
-#define SFL_WAVE_OCC 6  // waves per SIMD the one-env-per-wave kernel is register-budgeted for (6: 80 VGPRs)
-#endif
+SFL_KWAVE_V7(extern template)      // (defined in sfl_kwave_v7.hip)
+SFL_KWAVE_HPG(extern template)     // (hyperparameter groups: defined in sfl_kwave_hpg.hip)
+SFL_KWAVE_HPG_V7(extern template)  // (defined in sfl_kwave_hpg_v7.hip)
 
 namespace {
 
@@ -44,30 +42,13 @@ __global__ void __launch_bounds__(256) k_run_ext(const sfl::SflMap* __restrict__
   if (e < s->E) sfl::env_run_ext<NW>(*m, *s, *c, e);
 }
 
-// One env per wavefront (sfl_wave.h): 4 envs per block.  PPL / SPL = semaphore / counter
-// registers per lane (sfl::kVariants).
-// TIMED: the learn() / test() instantiation, with the sampled phase timers (sfl_wave.h PhaseTimer); the
-// benchmark's sfl_step runs the untimed one
-template <int PPL, int SPL, int TW, bool TRACE, bool TIMED = false>
-__global__ void __launch_bounds__(SFL_WAVE_BLOCK) __attribute__((amdgpu_waves_per_eu(SFL_WAVE_OCC))) k_wave(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict__ s,
-                                              const sfl::SflCtl* __restrict__ c) {
-  sfl::wave::run<PPL, SPL, TW, TRACE, false, TIMED>(*m, *s, *c);
-}
-// several envs per wavefront: k_wave_g (sfl_kwave_g.h).  Variant 7 -- the bench's c3 shape -- is compiled in
-// its own translation unit (sfl_kwave_v7.hip) with another register-allocation-aware scheduler; this one
-// only declares it (below the includes).
+// One env per wavefront: k_wave / k_wave2; several envs per wavefront: k_wave_g (all in sfl_kwave_g.h).  Variant 7
+// of k_wave_g -- the bench's c3 shape -- is compiled in its own translation unit (sfl_kwave_v7.hip) with another
+// register-allocation-aware scheduler, and the kernels of handles with hyperparameter groups (HPG) in
+// sfl_kwave_hpg.hip / sfl_kwave_hpg_v7.hip; this unit only declares those (below the includes).
+using sflk::k_wave;
+using sflk::k_wave2;
 using sflk::k_wave_g;
-// maps with 65-128 trains (two train slots per lane): one env per 64-thread block (its LDS is
-// ~22 KB), register budget for the LDS-bound occupancy of 2 waves per SIMD
-#ifndef SFL_WAVE2_OCC
-#define SFL_WAVE2_OCC (SFL_PF_RING64 > 0 ? 4 : 2)  // waves per SIMD k_wave2 is register-budgeted for
-#endif
-template <int PPL, int SPL, int TW, bool TRACE, bool TIMED = false>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SFL_WAVE2_OCC))) k_wave2(const sfl::SflMap* __restrict__ m,
-                                                                                   const sfl::SflState* __restrict__ s,
-                                                                                   const sfl::SflCtl* __restrict__ c) {
-  sfl::wave::run<PPL, SPL, TW, TRACE, false, TIMED>(*m, *s, *c);
-}
 
 // graph-partitioned rounds, local env step on the one-env-per-wave body (sfl_wave.h, PART)
 template <int PPL, int SPL, int TW>
@@ -641,17 +622,22 @@ struct HipBackend {
     const auto* ps = (const sfl::SflState*)(base + os);
     const auto* pc = (const sfl::SflCtl*)(base + oc);
     const unsigned wblocks = (unsigned)(((size_t)s.E * 64 + SFL_WAVE_BLOCK - 1) / SFL_WAVE_BLOCK);
+    // hyperparameter groups: the HPG instantiation, plain only (the engine refuses a trace and passes no phase
+    // counters on a grouped handle); k_run reads the map's group pointer at run time
+    const bool hpg = m.env_group != nullptr;
 #define SFL_KW(v)                                                                                                   \
   {                                                                                                             \
     constexpr sfl::WaveShape w = sfl::kVariants[v];                                                             \
-    if (c.trace) k_wave<w.PPL, w.SPL, w.TW, true><<<wblocks, SFL_WAVE_BLOCK, 0, stream>>>(pm, ps, pc);          \
+    if (hpg) k_wave<w.PPL, w.SPL, w.TW, false, false, true><<<wblocks, SFL_WAVE_BLOCK, 0, stream>>>(pm, ps, pc); \
+    else if (c.trace) k_wave<w.PPL, w.SPL, w.TW, true><<<wblocks, SFL_WAVE_BLOCK, 0, stream>>>(pm, ps, pc);     \
     else if (c.phase_cyc) k_wave<w.PPL, w.SPL, w.TW, false, true><<<wblocks, SFL_WAVE_BLOCK, 0, stream>>>(pm, ps, pc); \
     else k_wave<w.PPL, w.SPL, w.TW, false><<<wblocks, SFL_WAVE_BLOCK, 0, stream>>>(pm, ps, pc);                 \
   }
 #define SFL_KW2(v)                                                                                       \
   {                                                                                                             \
     constexpr sfl::WaveShape w = sfl::kVariants[v];                                                             \
-    if (c.trace) k_wave2<w.PPL, w.SPL, w.TW, true><<<s.E, 64, 0, stream>>>(pm, ps, pc);                         \
+    if (hpg) k_wave2<w.PPL, w.SPL, w.TW, false, false, true><<<s.E, 64, 0, stream>>>(pm, ps, pc);               \
+    else if (c.trace) k_wave2<w.PPL, w.SPL, w.TW, true><<<s.E, 64, 0, stream>>>(pm, ps, pc);                    \
     else if (c.phase_cyc) k_wave2<w.PPL, w.SPL, w.TW, false, true><<<s.E, 64, 0, stream>>>(pm, ps, pc);         \
     else k_wave2<w.PPL, w.SPL, w.TW, false><<<s.E, 64, 0, stream>>>(pm, ps, pc);                                \
   }
@@ -659,7 +645,8 @@ struct HipBackend {
   {                                                                                                             \
     constexpr sfl::WaveShape w = sfl::kVariants[v];                                                             \
     const unsigned gblocks = (unsigned)(((size_t)s.E * w.G + SFL_GROUP_BLOCK - 1) / SFL_GROUP_BLOCK);             \
-    if (c.trace) k_wave_g<w.PPL, w.SPL, w.TW, true, w.G, w.OCC, false, (bool)w.LM><<<gblocks, SFL_GROUP_BLOCK, 0, stream>>>(pm, ps, pc); \
+    if (hpg) k_wave_g<w.PPL, w.SPL, w.TW, false, w.G, w.OCC, false, (bool)w.LM, true><<<gblocks, SFL_GROUP_BLOCK, 0, stream>>>(pm, ps, pc); \
+    else if (c.trace) k_wave_g<w.PPL, w.SPL, w.TW, true, w.G, w.OCC, false, (bool)w.LM><<<gblocks, SFL_GROUP_BLOCK, 0, stream>>>(pm, ps, pc); \
     else if (c.phase_cyc)                                                                                       \
       k_wave_g<w.PPL, w.SPL, w.TW, false, w.G, w.OCC, true, (bool)w.LM><<<gblocks, SFL_GROUP_BLOCK, 0, stream>>>(pm, ps, pc); \
     else k_wave_g<w.PPL, w.SPL, w.TW, false, w.G, w.OCC, false, (bool)w.LM><<<gblocks, SFL_GROUP_BLOCK, 0, stream>>>(pm, ps, pc); \

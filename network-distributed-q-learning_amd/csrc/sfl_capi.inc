@@ -274,4 +274,9 @@ int sfl_part_get_q(sfl_handle* h, uint32_t global_env, double* q, uint32_t* touc
   return sfl::part_get_q(HH(h), global_env, q, touched);
 }
 
+int sfl_set_hparam_groups(sfl_handle* h, int32_t n_groups, const sfl_hparam_group* groups, const uint16_t* env_group) {
+  if (!h) return sfl::fail("sfl_set_hparam_groups: null handle");
+  return sfl::set_hparam_groups(HH(h), n_groups, groups, env_group);
+}
+
 }  // extern "C"

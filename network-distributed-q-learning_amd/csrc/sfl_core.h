@@ -107,7 +107,16 @@ struct SflMap {
   // step t (row t - 1) of an episode, 0 = none; mf_steps == 0: the counter-based draw (mf_draw)
   const uint8_t* mf_tab;
   int32_t mf_steps;
+  // hyperparameter groups (sfl_set_hparam_groups): env e learns with the epsilon / lr schedule of group
+  // env_group[e]; env_group == null: every env with the map's own eps0 ... lr_tab above.  gamma, default_q,
+  // max_steps and ntab are never grouped.
+  int32_t n_groups;
+  const uint16_t* env_group;  // [E]
+  const double* hpg_eps_tab;  // [n_groups][ntab]
+  const double* hpg_lr_tab;   // [n_groups][ntab]
+  const double* hpg_sc;       // [n_groups][4]: HPG_EPS0, HPG_EPS_DECAY, HPG_LR0, HPG_LR_DECAY
 };
+enum : int { HPG_EPS0 = 0, HPG_EPS_DECAY = 1, HPG_LR0 = 2, HPG_LR_DECAY = 3 };
 
 // x % n for 1 <= n < 2^32 with M = floor((2^64 - 1) / n): q = hi64(x * M) is floor(x / n) or one less (M is
 // within 1 of 2^64 / n and x < 2^64), so one correction makes the remainder exact.  On the GPU the 64-bit `%`
@@ -568,13 +577,30 @@ struct Env {
     const uint32_t row = m.row_base[4 * sw + slot] + state;
     s.touched[(size_t)e * m.touched_words + (row >> 5)] |= 1u << (row & 31u);
   }
-  SFL_FN double eps_of(uint32_t n) const { return n < (uint32_t)m.ntab ? m.eps_tab[n] : m.eps0 * pow(m.eps_decay, (double)n); }
+  // hyperparameter groups (SflMap::env_group): the env's group's table rows and scalars, else the map's own
+  SFL_FN double eps_of(uint32_t n) const {
+    if (m.env_group) {
+      const size_t g = m.env_group[e];
+      if (n < (uint32_t)m.ntab) return m.hpg_eps_tab[g * (uint32_t)m.ntab + n];
+      return m.hpg_sc[g * 4 + HPG_EPS0] * pow(m.hpg_sc[g * 4 + HPG_EPS_DECAY], (double)n);
+    }
+    return n < (uint32_t)m.ntab ? m.eps_tab[n] : m.eps0 * pow(m.eps_decay, (double)n);
+  }
   // beyond the table: eps only decides `random() < eps` (an ulp of pow moves that by ~1e-17 in
   // probability), but lr enters the Q values, so on the device a decaying lr past the table is an error
-  SFL_FN double lr_of(uint32_t n, uint32_t& e) const {
+  SFL_FN double lr_of(uint32_t n, uint32_t& err) const {
+    if (m.env_group) {
+      const size_t g = m.env_group[e];
+      if (n < (uint32_t)m.ntab) return m.hpg_lr_tab[g * (uint32_t)m.ntab + n];
+      const double lr_decay = m.hpg_sc[g * 4 + HPG_LR_DECAY];
+#if defined(__HIP_DEVICE_COMPILE__)
+      if (lr_decay != 1.0) err |= E_LR_TABLE;
+#endif
+      return m.hpg_sc[g * 4 + HPG_LR0] * pow(lr_decay, (double)n);
+    }
     if (n < (uint32_t)m.ntab) return m.lr_tab[n];
 #if defined(__HIP_DEVICE_COMPILE__)
-    if (m.lr_decay != 1.0) e |= E_LR_TABLE;
+    if (m.lr_decay != 1.0) err |= E_LR_TABLE;
 #endif
     return m.lr0 * pow(m.lr_decay, (double)n);
   }

@@ -506,6 +506,64 @@ int set_mf_schedule(Handle<B>* h, int32_t steps, const uint8_t* table) {
   return h->be.sync() ? fail(h->be.error()) : 0;
 }
 
+// Hyperparameter groups (include/sfl.h sfl_set_hparam_groups): the groups' tables as [n_groups][ntab], their
+// scalars as [n_groups][4] (HPG_*) and env_group[E] in device memory; the kernels read them from the next launch.
+// Everything is validated on the host before anything is uploaded; a refused call leaves the handle as it was.
+template <class B>
+int set_hparam_groups(Handle<B>* h, int32_t n_groups, const sfl_hparam_group* groups, const uint16_t* env_group) {
+  if (h->part.world) return fail("sfl_set_hparam_groups: the handle is graph-partitioned");
+  if (h->env_mode) return fail("sfl_set_hparam_groups: the handle is in external-action mode (no learner)");
+  if (n_groups < 0 || n_groups > SFL_MAX_HPARAM_GROUPS)
+    return fail("sfl_set_hparam_groups: n_groups outside [0, " + std::to_string(SFL_MAX_HPARAM_GROUPS) + "]");
+  SflMap& m = h->map;
+  const size_t ntab = m.ntab > 0 ? (size_t)m.ntab : 0, G = (size_t)n_groups, E = h->E;
+  const double *d_eps = nullptr, *d_lr = nullptr, *d_sc = nullptr;
+  const uint16_t* d_eg = nullptr;
+  if (n_groups > 0) {
+    if (!groups || !env_group) return fail("sfl_set_hparam_groups: null groups or env_group");
+    for (size_t g = 0; g < G; ++g)
+      if (ntab && (!groups[g].eps_tab || !groups[g].lr_tab))
+        return fail("sfl_set_hparam_groups: group " + std::to_string(g) + " has a null table");
+    for (size_t e = 0; e < E; ++e)
+      if (env_group[e] >= n_groups)
+        return fail("sfl_set_hparam_groups: env " + std::to_string(e) + " is in group " + std::to_string(env_group[e]) +
+                    " of " + std::to_string(n_groups));
+    std::vector<double> eps(G * ntab), lr(G * ntab), sc(G * 4);
+    for (size_t g = 0; g < G; ++g) {
+      if (ntab) {
+        memcpy(&eps[g * ntab], groups[g].eps_tab, ntab * 8);
+        memcpy(&lr[g * ntab], groups[g].lr_tab, ntab * 8);
+      }
+      sc[g * 4 + HPG_EPS0] = groups[g].epsilon;
+      sc[g * 4 + HPG_EPS_DECAY] = groups[g].epsilon_decay_rate;
+      sc[g * 4 + HPG_LR0] = groups[g].lr;
+      sc[g * 4 + HPG_LR_DECAY] = groups[g].lr_decay_rate;
+    }
+    d_eps = h->upload(eps.data(), eps.size());
+    d_lr = h->upload(lr.data(), lr.size());
+    d_sc = h->upload(sc.data(), sc.size());
+    d_eg = h->upload(env_group, E);
+    const bool ok = d_eps && d_lr && d_sc && d_eg && h->be.sync() == 0;  // (the host sources live until here)
+    if (!ok) {
+      for (const void* p : {(const void*)d_eps, (const void*)d_lr, (const void*)d_sc, (const void*)d_eg})
+        if (p) h->dfree((void*)p);
+      return fail(std::string("sfl_set_hparam_groups: device allocation or upload failed") +
+                  (h->be.error()[0] ? std::string(": ") + h->be.error() : std::string()));
+    }
+  } else if (h->be.sync()) {
+    return fail(h->be.error());
+  }
+  // (synchronous API: no launch of the handle is in flight, the old arrays can go)
+  for (const void* p : {(const void*)m.hpg_eps_tab, (const void*)m.hpg_lr_tab, (const void*)m.hpg_sc, (const void*)m.env_group})
+    if (p) h->dfree((void*)p);
+  m.n_groups = n_groups;
+  m.hpg_eps_tab = d_eps;
+  m.hpg_lr_tab = d_lr;
+  m.hpg_sc = d_sc;
+  m.env_group = d_eg;
+  return 0;
+}
+
 template <class B>
 int part_host_access(Handle<B>* h, bool write);
 
@@ -633,6 +691,10 @@ template <class B>
 int run(Handle<B>* h, const SflCtl& c_in, sfl_run_args* args) {
   if (h->part.world) return fail("sfl_run: the handle is graph-partitioned; drive it with sfl_part_*");
   if (h->env_mode) return fail("sfl_run: the handle is in external-action mode (sfl_env_begin); drive it with sfl_env_step");
+  // (the grouped kernels are built plain only: no traced and no phase-timed instantiation)
+  const bool grouped = h->map.env_group != nullptr;
+  if (grouped && args && args->trace && args->trace_cap > 0)
+    return fail("sfl_run: a per-decision trace is not available on a handle with hyperparameter groups");
   SflCtl c = c_in;
   const size_t E = h->E, T = h->map.T;
   const int32_t cap = args ? args->stats_cap : 0;
@@ -664,7 +726,7 @@ int run(Handle<B>* h, const SflCtl& c_in, sfl_run_args* args) {
   c.launch_dec = h->d_launch_dec;
   c.launch_ticks = h->d_launch_ticks;
   c.launch_bytes = h->d_launch_bytes;
-  c.phase_cyc = args ? h->d_phase : nullptr;  // learn / test (not the benchmark's sfl_step): phase timers
+  c.phase_cyc = args && !grouped ? h->d_phase : nullptr;  // learn / test (not the benchmark's sfl_step): phase timers
   uint64_t* d_trace = nullptr;
   uint64_t* d_trace_n = nullptr;
   if (args && args->trace && args->trace_cap > 0) {
@@ -709,6 +771,7 @@ int run(Handle<B>* h, const SflCtl& c_in, sfl_run_args* args) {
 template <class B>
 int env_begin(Handle<B>* h) {
   if (h->part.world) return fail("sfl_env_begin: the handle is graph-partitioned");
+  if (h->map.env_group) return fail("sfl_env_begin: the handle has hyperparameter groups (sfl_set_hparam_groups)");
   const size_t E = h->E, T = h->map.T, S = h->map.S, NP = h->map.NP;
   if (!h->d_ext) {
     SflExt& x = h->ext;
@@ -810,6 +873,7 @@ int part_config(Handle<B>* h, int rank, int world, const int32_t* owner, uint32_
                 uint32_t cap_req, uint32_t cap_upd) {
   if (world < 1 || rank < 0 || rank >= world || world > 255) return fail("sfl_part_config: bad rank / world");
   if (h->part.world) return fail("sfl_part_config: already configured");
+  if (h->map.env_group) return fail("sfl_part_config: the handle has hyperparameter groups (sfl_set_hparam_groups)");
   if (env_base + h->E > E_tot) return fail("sfl_part_config: env range outside envs_total");
   if (cap_req < h->E) return fail("sfl_part_config: request capacity must hold one request per local env");
   if (cap_upd < 1 || (uint64_t)cap_req + cap_upd >= (1ull << 31) || (uint64_t)world * (cap_req + cap_upd + 1ull) >= (1ull << 32))

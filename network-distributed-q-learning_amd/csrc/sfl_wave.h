@@ -327,8 +327,11 @@ struct PortRec {
 // applied in the next (with the owner's reply), and the post step's Q operations are update
 // records to the owners
 // LM (run_groups only, sfl_engine.h variant 11): the map's move table and distance map (int16) live in the block's LDS
-template <int PPL, int SPL, int TWc, bool PART = false, int G = 64, bool LM = false>
+// HPG: hyperparameter groups (sfl_set_hparam_groups): the env's epsilon and lr schedule are its group's -- row
+// env_group[e] of the [n_groups][ntab] tables and of the [n_groups][4] scalars -- instead of the map's own
+template <int PPL, int SPL, int TWc, bool PART = false, int G = 64, bool LM = false, bool HPG = false>
 struct WEnv {
+  static_assert(!(HPG && PART), "hyperparameter groups are not part of the partitioned local step");
   static_assert(G == 64 || G == 32 || G == 16 || G == 8, "lane group of 8, 16, 32 or 64 lanes");
   static_assert(G == 64 || !PART, "the partitioned local step runs one env per wavefront");
   const SflMap& m;
@@ -349,7 +352,8 @@ struct WEnv {
   static constexpr bool RING = !PART && TPL > 1 && RING_N > 0 && RING_N < TWc;
   static constexpr int PF_SLOTS = PART ? 1 : (RING ? RING_N : TWc);
   // (SFL_EPS_PF) the record's doubles: + the staged epsilon
-  static constexpr bool EPS_PF = SFL_EPS_PF && !PART && G < 64 && G * SPL <= 64;
+  // (HPG: the staging reads the map's own table, so grouped handles decide on the loaded value)
+  static constexpr bool EPS_PF = SFL_EPS_PF && !PART && G < 64 && G * SPL <= 64 && !HPG;
   static constexpr int PFD = EPS_PF ? PF_D + 1 : PF_D;
   static constexpr int PFW = 2 * PFD + PF_WI;
   __device__ __forceinline__ static int pfx(int h) { return PART ? 0 : h; }
@@ -394,6 +398,7 @@ struct WEnv {
   uint32_t pf_qoff[PFS];  // offset of the staged pending cell (PF_NONE: none)
   bool pf_ok;        // uniform: this batch has been prefetched
   uint32_t lerr;  // error bits seen by this lane (OR-reduced on store)
+  uint32_t hgrp = 0;  // HPG: the env's hyperparameter group (G = 64: wave-uniform, in an SGPR), loaded by load()
   // this env's blocks: Q-table, key-set bitmap, (switch, train) slots (env-major [T][S] here,
   // so one env's slots are contiguous and a flush over switches is one coalesced access)
   double* qb;
@@ -833,18 +838,51 @@ struct WEnv {
     __hip_atomic_fetch_or((SFL_AS_G uint32_t*)tbase() + (row >> 5), 1u << (row & 31u), __ATOMIC_RELAXED,
                           __HIP_MEMORY_SCOPE_AGENT);
   }
+  // HPG: the env's rows of the grouped tables, and scalar k of its group (HPG_EPS0 ...: SflMap::hpg_sc).  The
+  // group is group-uniform, so G = 64 reads them with scalar loads and G < 64 with vector loads (LDC)
+  __device__ __forceinline__ const double* eps_row() const {
+    if constexpr (HPG) return m.hpg_eps_tab + (size_t)hgrp * (uint32_t)m.ntab;
+    else return m.eps_tab;
+  }
+  __device__ __forceinline__ const double* lr_row() const {
+    if constexpr (HPG) return m.hpg_lr_tab + (size_t)hgrp * (uint32_t)m.ntab;
+    else return m.lr_tab;
+  }
+  __device__ __forceinline__ double hsc(int k) const { return LDC(m.hpg_sc, (size_t)hgrp * 4u + (uint32_t)k); }
+  __device__ __forceinline__ double eps0_() const {
+    if constexpr (HPG) return hsc(HPG_EPS0);
+    else return m.eps0;
+  }
+  __device__ __forceinline__ double eps_decay_() const {
+    if constexpr (HPG) return hsc(HPG_EPS_DECAY);
+    else return m.eps_decay;
+  }
   // (a decaying lr past the table is an error, E_LR_TABLE: see SflEnv::lr_of in sfl_core.h)
+  // HPG: the table first -- a group with lr_decay == 1.0 holds lr0 * 1.0**n == lr0 in every entry, so the result
+  // is the shortcut's without a load of the group's lr_decay per update; the group's scalars only past the table
   __device__ __forceinline__ double lr_of(uint32_t n) {
-    if (m.lr_decay == 1.0) return m.lr0;  // lr0 * 1.0**n (distr_q.py:70-79)
-    if (n < (uint32_t)m.ntab) return LDC(m.lr_tab, (size_t)n);
-    lerr |= E_LR_TABLE;
-    return m.lr0;
+    if constexpr (HPG) {
+      if (n < (uint32_t)m.ntab) return LDC(lr_row(), (size_t)n);
+      if (hsc(HPG_LR_DECAY) != 1.0) lerr |= E_LR_TABLE;
+      return hsc(HPG_LR0);
+    } else {
+      if (m.lr_decay == 1.0) return m.lr0;  // lr0 * 1.0**n (distr_q.py:70-79)
+      if (n < (uint32_t)m.ntab) return LDC(m.lr_tab, (size_t)n);
+      lerr |= E_LR_TABLE;
+      return m.lr0;
+    }
   }
   __device__ __forceinline__ double lr_of_var(uint32_t n) {
-    if (m.lr_decay == 1.0) return m.lr0;
-    if (n < (uint32_t)m.ntab) return ld(m.lr_tab, (size_t)n);
-    lerr |= E_LR_TABLE;
-    return m.lr0;
+    if constexpr (HPG) {
+      if (n < (uint32_t)m.ntab) return ld(lr_row(), (size_t)n);
+      if (hsc(HPG_LR_DECAY) != 1.0) lerr |= E_LR_TABLE;
+      return hsc(HPG_LR0);
+    } else {
+      if (m.lr_decay == 1.0) return m.lr0;
+      if (n < (uint32_t)m.ntab) return ld(m.lr_tab, (size_t)n);
+      lerr |= E_LR_TABLE;
+      return m.lr0;
+    }
   }
 
   // ---- launch-boundary state transfer ---------------------------------------------------------
@@ -955,6 +993,7 @@ struct WEnv {
       n_dec = 0;
       return;
     }
+    if constexpr (HPG) hgrp = U((uint32_t)ld(m.env_group, (size_t)e));
     now = U(ld(s.elapsed, e));
     flags = U(ld(s.eflags, e));
     epoch = U(ld(s.epoch, e));
@@ -1904,7 +1943,7 @@ struct WEnv {
       // eps0 * decay**n (distr_q.py:59-68): host-computed table (a scalar load, K$-resident), pow beyond it
       const double ud = Ud(pcg_double(rng));
       if (xp::kEpsConst) {
-        explore = ud < m.eps0;
+        explore = ud < eps0_();
       } else {
         // (EPS_PF) the staged value, unless the switch was decided on since the staging (its count moved)
         bool staged = false;
@@ -1914,7 +1953,7 @@ struct WEnv {
           eps_st = pfh[3];
         }
         explore = ud < (staged ? eps_st
-                               : (n < (uint32_t)m.ntab ? LDC(m.eps_tab, (size_t)n) : m.eps0 * pow_ool(m.eps_decay, (double)n)));
+                               : (n < (uint32_t)m.ntab ? LDC(eps_row(), (size_t)n) : eps0_() * pow_ool(eps_decay_(), (double)n)));
       }
       if (explore && !observe_only) {
         const uint32_t sub_seed = pcg_bounded(rng, 2147483646u);
@@ -2397,9 +2436,9 @@ struct PhaseTimer {
   }
 };
 
-template <int PPL, int SPL, int TW, bool TRACE, bool PART = false, bool TIMED = false>
+template <int PPL, int SPL, int TW, bool TRACE, bool PART = false, bool TIMED = false, bool HPG = false>
 __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const SflPart* P = nullptr) {
-  using V = WEnv<PPL, SPL, TW, PART>;
+  using V = WEnv<PPL, SPL, TW, PART, 64, false, HPG>;
   // semaphores, counters, prefetch records, rng, timetable (PART: one record, timetable from the map)
   // (PART: the launch's initial records / counters in place of the timetable copy)
   constexpr int LDS_WORDS =
@@ -2597,9 +2636,9 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
 // follow it -- as a flat loop in which each iteration advances every group by at most one tick,
 // one post step and one decision.  The groups of a wave diverge (one ticks while another decides);
 // a batch loop as in run() would hold every group until the longest batch of the wave is done.
-template <int PPL, int SPL, int TW, bool TRACE, int G, bool TIMED = false, bool LM = false>
+template <int PPL, int SPL, int TW, bool TRACE, int G, bool TIMED = false, bool LM = false, bool HPG = false>
 __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) {
-  using V = WEnv<PPL, SPL, TW, false, G, LM>;
+  using V = WEnv<PPL, SPL, TW, false, G, LM, HPG>;
   // per env: semaphores, counters, prefetch records, rng; per block: the timetable rows and the
   // per-switch / per-port map records (the groups of a wave read different switches' records: LDS
   // reads instead of vector loads)

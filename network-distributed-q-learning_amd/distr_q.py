@@ -10,13 +10,18 @@ the same output files (distr_q.py:237-239, 287-294, 368-375):
 With ``env.n_envs == 1`` the files have exactly the reference's shapes; with a batch
 of E envs (the MI355X use case: a seed sweep in lock-step) every array gets a leading
 env axis and env e runs with seed ``seed + e``.
+
+A hyperparameter sweep in one batch (hyperparam_tuning.py): ``hparam_groups`` / ``env_group`` give every env its
+group's epsilon and lr schedule (runtime.Batch), ``seeds`` explicit per-env seeds (a sweep runs every group on the
+same seeds), and ``outputs`` splits the batch into learners that each write their own directory: ``learn`` then
+writes, per ``(subdir, envs)``, the files a learner holding just those envs writes, checkpoints included.
 """
 from __future__ import annotations
 
 import os
 import pickle
 import time
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -26,7 +31,9 @@ from .env import ASyncSwitchEnv
 
 class DistrQLearning:
     def __init__(self, env: ASyncSwitchEnv, gamma=1.0, epsilon=0.4, epsilon_decay_rate=0.0, lr=0.4,
-                 lr_decay_rate=0.0, default_q=0.0, seed=450565, lib=None):
+                 lr_decay_rate=0.0, default_q=0.0, seed=450565, lib=None, seeds: Optional[Sequence[int]] = None,
+                 hparam_groups: Optional[Sequence[dict]] = None, env_group: Optional[Sequence[int]] = None,
+                 outputs: Optional[Sequence[Tuple[str, Sequence[int]]]] = None):
         self.env = env
         self.gamma = gamma
         self.initial_epsilon = epsilon
@@ -39,10 +46,20 @@ class DistrQLearning:
         self.destination_bonus = 1000.0
         self.hp = dict(gamma=gamma, epsilon=epsilon, epsilon_decay_rate=epsilon_decay_rate, lr=lr,
                        lr_decay_rate=lr_decay_rate, default_q=default_q)
-        seeds = [int(seed) + e for e in range(env.n_envs)]
+        if seeds is None:
+            seeds = [int(seed) + e for e in range(env.n_envs)]
+        elif len(seeds) != env.n_envs:
+            raise ValueError(f"seeds: {len(seeds)} seeds for the env's {env.n_envs} envs")
+        # the learners the batch is written out as: (subdirectory of learn's out_dir, env indices)
+        self.outputs = [("", list(range(env.n_envs)))] if outputs is None else [(str(d), [int(e) for e in es])
+                                                                                for d, es in outputs]
+        for _, es in self.outputs:
+            if not es or min(es) < 0 or max(es) >= env.n_envs:
+                raise ValueError("outputs: every learner needs at least one env of the batch")
         self.batch = runtime.Batch(env.compiled, self.hp, seeds, lib=lib, device=env.device, max_steps=env.max_steps,
                                    malfunction_stream=getattr(env, "malfunction_stream", "counter"),
-                                   delay_threshold=getattr(env, "delay_threshold", 20))
+                                   delay_threshold=getattr(env, "delay_threshold", 20), hparam_groups=hparam_groups,
+                                   env_group=env_group)
 
     # ------------------------------------------------------------------
     @property
@@ -58,6 +75,21 @@ class DistrQLearning:
 
     def _save(self, out_dir, name, arr):
         np.savez_compressed(os.path.join(out_dir, name), x=arr)
+
+    def _save_envs(self, out_dir, name, a, delays=False):
+        """An [episode, (train,) env] array, per output learner in its envs' reference shape."""
+        a = np.moveaxis(np.asarray(a, dtype=np.float64) if delays else np.asarray(a), -1, 0)  # [E, episode(, train)]
+        for sub, envs in self.outputs:
+            self._save(os.path.join(out_dir, sub), name, a[envs[0]] if len(envs) == 1 else a[envs])
+
+    def _save_each(self, out_dir, name, make):
+        """``make(envs)``'s array into every output learner's directory."""
+        for sub, envs in self.outputs:
+            self._save(os.path.join(out_dir, sub), name, make(envs))
+
+    def _save_q(self, out_dir, name):
+        for sub, envs in self.outputs:
+            self.save(os.path.join(out_dir, sub, name), envs=envs)
 
     def _timing(self, t0):
         """The reference's accumulators (switch_env.py:67-73, distr_q.py:271-273, 304-358), from the device's
@@ -90,6 +122,9 @@ class DistrQLearning:
         b = self.batch
         E, T = b.E, b.cm.T
         f = int(exploit_freq or 0)
+        for sub, _ in self.outputs:
+            if sub:
+                os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
         b.learn_begin()
         pre = None
         if f == 1 and num_episodes > 0:
@@ -129,13 +164,13 @@ class DistrQLearning:
                     x = b.test(1)
                     b.lib.check(b.lib.dll.sfl_mark_exploit_done(b.h), "sfl_mark_exploit_done")
                     pre_x[t] = (x["cum_reward"][0], x["arrived"][0])
-                self.save(os.path.join(out_dir, f"checkpoint_{t + 1}.pkl"))
-                self._save(out_dir, f"cum_reward_checkpoint_{t + 1}.npz", self._env_major(cum))
-                self._save(out_dir, f"arrived_trains_checkpoint_{t + 1}.npz", self._env_major(arrived[:t]))
-                self._save(out_dir, f"delays_checkpoint_{t + 1}.npz", self._env_major(delays[:t], delays=True))
+                self._save_q(out_dir, f"checkpoint_{t + 1}.pkl")
+                self._save_envs(out_dir, f"cum_reward_checkpoint_{t + 1}.npz", cum)
+                self._save_envs(out_dir, f"arrived_trains_checkpoint_{t + 1}.npz", arrived[:t])
+                self._save_envs(out_dir, f"delays_checkpoint_{t + 1}.npz", delays[:t], delays=True)
                 # the reference resets trains_at_destination just before saving it (distr_q.py:285 vs 293)
-                self._save(out_dir, f"trains_at_dest_checkpoint_{t + 1}.npz", np.array([]))
-                self._save(out_dir, f"num_malfunctions_checkpoint_{t + 1}.npz", self._env_major(mfs[:t]))
+                self._save_each(out_dir, f"trains_at_dest_checkpoint_{t + 1}.npz", lambda envs: np.array([]))
+                self._save_envs(out_dir, f"num_malfunctions_checkpoint_{t + 1}.npz", mfs[:t])
                 if qinit_pending:
                     b.apply_qinit()
                     qinit_pending = False
@@ -145,36 +180,27 @@ class DistrQLearning:
         for t, (c_, a_) in pre_x.items():  # (the kernel's rows for these episodes were not written)
             cum_x[t] = c_
             arr_x[t] = a_
-        self._save(out_dir, "cum_reward.npz", self._env_major(cum))
-        self._save(out_dir, "arrived_trains.npz", self._env_major(arrived))
-        self._save(out_dir, "delays.npz", self._env_major(delays, delays=True))
-        self._save(out_dir, "trains_at_dest.npz", self._trains_at_dest())
-        self._save(out_dir, "num_malfunctions.npz", self._env_major(mfs))
+        self._save_envs(out_dir, "cum_reward.npz", cum)
+        self._save_envs(out_dir, "arrived_trains.npz", arrived)
+        self._save_envs(out_dir, "delays.npz", delays, delays=True)
+        self._save_each(out_dir, "trains_at_dest.npz", self._trains_at_dest)
+        self._save_envs(out_dir, "num_malfunctions.npz", mfs)
         if f:
             sel = (np.arange(num_episodes) + 1) % f == 0
-            self._save(out_dir, "cum_reward_exploit.npz", self._env_major(cum_x[sel]))
-            self._save(out_dir, "arrived_trains_exploit.npz", self._env_major(arr_x[sel]))
+            self._save_envs(out_dir, "cum_reward_exploit.npz", cum_x[sel])
+            self._save_envs(out_dir, "arrived_trains_exploit.npz", arr_x[sel])
         self.env.num_malfunctions = self._squeeze(mfs[-1]) if num_episodes else 0
         self._timing(t0)
         return dict(cum_reward=cum, arrived_trains=arrived, delays=delays, num_malfunctions=mfs,
                     cum_reward_exploit=cum_x, arrived_trains_exploit=arr_x)
 
-    def _env_major(self, a, delays=False):
-        """[episode, (train,) env] -> reference shape (E == 1) or env-leading axis."""
-        a = np.asarray(a)
-        if delays:
-            a = a.astype(np.float64)
-            a = np.moveaxis(a, -1, 0)  # [E, episode, train]
-        else:
-            a = np.moveaxis(a, -1, 0)  # [E, episode]
-        return a[0] if self.batch.E == 1 else a
-
-    def _trains_at_dest(self):
+    def _trains_at_dest(self, envs=None):
+        envs = range(self.batch.E) if envs is None else envs
         res = []
-        for e in range(self.batch.E):
+        for e in envs:
             _, _, _, _, tr_bits = self._env_state(e)
             res.append([h for h, bits in enumerate(tr_bits) if ((bits >> 2) & 7) == 6])
-        return np.array(res[0]) if self.batch.E == 1 else np.array(res, dtype=object)
+        return np.array(res[0]) if len(res) == 1 else np.array(res, dtype=object)
 
     def _env_state(self, e):
         import ctypes as C
@@ -211,11 +237,12 @@ class DistrQLearning:
         self._timing(t0)
         return cum, arrived, delays
 
-    def save(self, filename: str, mode: str = "pickle"):
-        """distr_q.py:492-508 — pickle of the Q dict (a list of dicts for a batch)."""
+    def save(self, filename: str, mode: str = "pickle", envs: Optional[Sequence[int]] = None):
+        """distr_q.py:492-508 — pickle of the Q dict (a list of dicts for a batch); ``envs``: of those envs only."""
         if mode != "pickle":
             raise NotImplementedError("only mode='pickle' is supported (the reference defines no csv/parquet dumper)")
-        obj = self.q_table if self.batch.E == 1 else self.q_tables()
+        envs = range(self.batch.E) if envs is None else envs
+        obj = self.batch.q_dict(envs[0]) if len(envs) == 1 else [self.batch.q_dict(e) for e in envs]
         with open(filename, "wb") as f:
             pickle.dump(obj, f)
 

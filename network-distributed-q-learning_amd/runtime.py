@@ -34,8 +34,12 @@ class Batch:
 
     def __init__(self, cm: CompiledMap, hp: dict, seeds: Sequence[int], lib: Optional[_lib.Lib] = None,
                  device: int = 0, max_steps: int = 100_000, ntab: int = NTAB, malfunction_stream: str = "counter",
-                 delay_threshold: int = 20):
-        """``malfunction_stream``: "counter" (the counter-based draw of the frozen Flatland spec,
+                 delay_threshold: int = 20, hparam_groups: Optional[Sequence[dict]] = None,
+                 env_group: Optional[Sequence[int]] = None):
+        """``hparam_groups`` / ``env_group``: hyperparameter groups (``set_hparam_groups``) -- env e learns with the
+        ``epsilon``, ``epsilon_decay_rate``, ``lr`` and ``lr_decay_rate`` of ``hparam_groups[env_group[e]]``; ``hp``
+        still gives ``gamma`` and ``default_q`` (and the schedule of an ungrouped batch).
+        ``malfunction_stream``: "counter" (the counter-based draw of the frozen Flatland spec,
         oracle/flatland_lite.py) or "flatland" (ParamMalfunctionGen's np_random draw order, mfstream.py).
         ``delay_threshold``: StandardObserver's (observer.py:221)."""
         self.cm = cm
@@ -102,6 +106,14 @@ class Batch:
             tab = mfstream.schedule(self.lib, sc, self.seeds)
             self.lib.check(self.lib.dll.sfl_set_mf_schedule(self.h, tab.shape[1], _ptr(tab, C.c_uint8)),
                            "sfl_set_mf_schedule")
+        self.hparam_groups: List[dict] = []
+        self.env_group: List[int] = []
+        if hparam_groups is not None or env_group is not None:
+            try:
+                self.set_hparam_groups(hparam_groups, env_group)
+            except Exception:
+                self.close()
+                raise
         self.learn_calls = 0
         self.timed_kernel_ms = 0.0  # device time of the learn / test launches (the phase-timed ones)
         self.trace_env = None
@@ -119,6 +131,44 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+    GROUP_KEYS = ("epsilon", "epsilon_decay_rate", "lr", "lr_decay_rate")
+
+    def set_hparam_groups(self, hparam_groups: Optional[Sequence[dict]], env_group: Optional[Sequence[int]] = None):
+        """Per-env hyperparameter groups (sfl_set_hparam_groups): env e learns with the epsilon and lr schedules of
+        ``hparam_groups[env_group[e]]`` (each a dict with ``GROUP_KEYS``; other keys are ignored -- gamma and
+        default_q stay the batch's) from the next launch on.  An empty / None ``hparam_groups`` returns every env to
+        the batch's own ``hp``."""
+        groups = [dict(g) for g in (hparam_groups or [])]
+        if not groups:
+            if env_group is not None and len(env_group):
+                raise ValueError("set_hparam_groups: env_group without hparam_groups")
+            self.lib.check(self.lib.dll.sfl_set_hparam_groups(self.h, 0, None, None), "sfl_set_hparam_groups")
+            self.hparam_groups, self.env_group = [], []
+            return
+        if env_group is None or len(env_group) != self.E:
+            raise ValueError(f"set_hparam_groups: env_group must name a group for each of the {self.E} envs")
+        eg = [int(g) for g in env_group]
+        if min(eg) < 0 or max(eg) > 0xFFFF:
+            raise ValueError("set_hparam_groups: env_group entries must be in [0, 65535]")
+        for g in groups:
+            missing = [k for k in self.GROUP_KEYS if k not in g]
+            if missing:
+                raise ValueError(f"set_hparam_groups: a group lacks {missing}")
+        ntab = len(self.eps_tab)
+        arr = (_lib.HParamGroup * len(groups))()
+        keep = []
+        for a, g in zip(arr, groups):
+            a.epsilon, a.epsilon_decay_rate = float(g["epsilon"]), float(g["epsilon_decay_rate"])
+            a.lr, a.lr_decay_rate = float(g["lr"]), float(g["lr_decay_rate"])
+            et = eps_table(g["epsilon"], g["epsilon_decay_rate"], ntab)
+            lt = lr_table(g["lr"], g["lr_decay_rate"], ntab)
+            keep += [et, lt]
+            a.eps_tab, a.lr_tab = _ptr(et, C.c_double), _ptr(lt, C.c_double)
+        ega = np.array(eg, dtype=np.uint16)
+        self.lib.check(self.lib.dll.sfl_set_hparam_groups(self.h, len(groups), arr, _ptr(ega, C.c_uint16)),
+                       "sfl_set_hparam_groups")
+        self.hparam_groups, self.env_group = groups, eg
 
     def _qinit_arrays(self):
         cm = self.cm
