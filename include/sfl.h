@@ -29,7 +29,10 @@
  *                     env.reset / agent_iter / last / step(action) / observe
  *                                                                    switchfl/switch_env.py:93, 616-675
  *                     (driven by any learner, e.g. distr_q.py:302-320)
- *   sfl_get_phase_cycles   the per-phase time accumulators            switchfl/switch_env.py:67-73
+ *   sfl_env_step_dev / sfl_env_sync   the same protocol for a policy on the device: device pointers in and
+ *                     out, the observation vector of observer.py:269-308 decoded on the device, queued on the
+ *                     caller's stream without a wait (the one call that is not synchronous)
+ *   sfl_get_phase_cycles  the per-phase time accumulators            switchfl/switch_env.py:67-73
  *                     (flatland_step_time, last_time, action_selection_time, update_time, reset_time ...)
  */
 #ifndef SFL_H
@@ -217,7 +220,9 @@ int sfl_get_sync_count(sfl_handle* h, uint64_t* waits, uint64_t* count_reads);
  * which its RCCL collectives follow).  Then sfl_part_owner returns without a
  * synchronisation, and so does sfl_part_local when requests_sent is null (its counts are read by
  * sfl_part_counts): the rounds between two sfl_part_counts calls queue without a synchronisation.
- * null: the handle's own stream again */
+ * null: the handle's own stream again; SFL_STREAM_DEFAULT: the device's default stream (whose own handle is
+ * the null pointer, e.g. torch's current stream when no other was chosen) */
+#define SFL_STREAM_DEFAULT ((void*)1)
 int sfl_set_stream(sfl_handle* h, void* stream);
 /* Which switches' rows the wave kernel decides on and updates in place: local_switches[S] (1 = in
  * place; only switches this rank owns), null = every switch this rank owns (the default after
@@ -262,6 +267,40 @@ typedef struct {
 } sfl_env_io;
 int sfl_env_begin(sfl_handle* h);
 int sfl_env_step(sfl_handle* h, sfl_env_io* io);
+
+/* ---- external-action mode with the policy on the device: tensors in and out, no host in the loop ----
+ * sfl_env_step_dev is sfl_env_step with every pointer in DEVICE memory (host memory on the host build): per
+ * env the same semantics (the action applied to the pending observation, the run to the next decision or the
+ * episode end, SFL_ACTION_RESET, a negative or null action re-emitting the pending observation, an action
+ * outside the switch's action space refused with E_BAD_ACTION and the observation emitted again).  The call is
+ * queued on the handle's current stream (the caller's after sfl_set_stream) and returns without waiting for
+ * the device: no stream or event synchronisation and, while the output pointers stay those of the previous call,
+ * no copy from host memory (the actions may come from a new buffer every call: they are copied device-to-device,
+ * in stream order, into the handle's own).  It returns -1 for argument and launch errors only; the envs' error flags (a
+ * refused action) surface at sfl_env_sync, which waits for the stream and reports them as sfl_env_step does.
+ * Device steps advance neither sfl_counters.last_kernel_ms nor the decisions counters (they are read on the
+ * host).  sfl_env_step and sfl_env_step_dev may be mixed on one handle: both act on the same env state, and
+ * a host call with null actions after device calls re-emits the pending observation into host memory.
+ *
+ * Besides the sfl_env_io fields the device call decodes the observation (observer.py:269-308) on the device:
+ * obs[e] = [r, c, sem[4], target[4][2], delay[4]] of the deciding switch, CompiledMap.obs_of_row padded to four
+ * ports: obs[0..1] the switch cell, obs[2 + j] sem[j], obs[6 + 2j], obs[7 + 2j] target[j], obs[14 + j] delay[j],
+ * all -1 for ports j >= the switch's port count.  When the episode ended in this call (agent == -1) the whole
+ * row is -1, the mask row 0, n_actions 0 and done 1.  obs must be 8-byte and action_mask 16-byte aligned. */
+#define SFL_OBS_WIDTH 18   /* r, c, sem[4], target[8], delay[4] */
+#define SFL_MAX_ACTIONS 16 /* a switch has up to 9 actions (8 routes + STOP); a row is one 16-byte store */
+typedef struct {
+  sfl_env_io io;         /* the same fields as the host call, but every non-null pointer is DEVICE memory */
+  int32_t* obs;          /* [n_envs][SFL_OBS_WIDTH], see above; null skips */
+  uint8_t* action_mask;  /* [n_envs][SFL_MAX_ACTIONS], 1 = allowed; null skips */
+  int32_t* n_actions;    /* [n_envs] the deciding switch's Discrete(n); 0 when the episode ended */
+  uint8_t* done;         /* [n_envs] 1 when agent == -1 (the episode ended in this call) */
+} sfl_env_dev_io;
+int sfl_env_step_dev(sfl_handle* h, const sfl_env_dev_io* io);
+int sfl_env_sync(sfl_handle* h);
+/* the two coordinate tables the observation decode reads, as derived at sfl_create from cell_sw and from
+ * tr_k / tr_target (debug / tests): switch_rc[S][2] and station_rc[K][2] as (row, column); null skips one */
+int sfl_get_obs_tables(sfl_handle* h, int32_t* switch_rc, int32_t* station_rc);
 /* Device time per phase of the learn loop since create, accumulated from in-kernel cycle counters of a
  * sample of the wavefronts (the kernels with one env per lane group; zero for the lane-per-env body):
  * cycles[0] tick (Flatland RailEnv.step + _move_trains / _check_active_switch), [1] observe (last()),

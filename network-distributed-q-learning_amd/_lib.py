@@ -77,6 +77,16 @@ class EnvIO(C.Structure):
                 ("malfunctions", P(C.c_int32)), ("delays", P(C.c_int32)), ("truncated", P(C.c_int32))]
 
 
+OBS_WIDTH = 18    # include/sfl.h SFL_OBS_WIDTH
+MAX_ACTIONS = 16  # include/sfl.h SFL_MAX_ACTIONS
+
+
+class EnvDevIO(C.Structure):
+    """sfl_env_dev_io (external-action mode, device pointers)."""
+    _fields_ = [("io", EnvIO), ("obs", P(C.c_int32)), ("action_mask", P(C.c_uint8)), ("n_actions", P(C.c_int32)),
+                ("done", P(C.c_uint8))]
+
+
 EXPORTS = {
     "sfl_abi_version": (C.c_int, []),
     "sfl_build_id": (C.c_char_p, []),
@@ -97,6 +107,9 @@ EXPORTS = {
     # external-action mode (aec.py) and the per-phase device time (distr_q.py timing accumulators)
     "sfl_env_begin": (C.c_int, [C.c_void_p]),
     "sfl_env_step": (C.c_int, [C.c_void_p, P(EnvIO)]),
+    "sfl_env_step_dev": (C.c_int, [C.c_void_p, P(EnvDevIO)]),
+    "sfl_env_sync": (C.c_int, [C.c_void_p]),
+    "sfl_get_obs_tables": (C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_int32)]),
     "sfl_get_phase_cycles": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_int32]),
     "sfl_get_env_state": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_int32), P(C.c_int32), P(C.c_uint64),
                                     P(C.c_int32), P(C.c_uint32)]),

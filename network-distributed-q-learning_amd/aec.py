@@ -7,7 +7,9 @@ env.last(); ...; env.step(action)``, driven by any learner (distr_q.py:302-320).
 ``sfl_env_begin`` / ``sfl_env_step`` (include/sfl.h): every call applies each env's action to the
 observation the previous call emitted and runs the env on to its next decision (or episode end), on the
 device, for all E envs at once.  ``ASyncSwitchEnv`` (env.py) wraps env 0 of an ``AECBatch`` in the
-reference's single-env methods.
+reference's single-env methods.  For a policy that lives on the same GPU, ``AECBatch.step_torch`` / ``sync``
+(``sfl_env_step_dev`` / ``sfl_env_sync``) are the same step with torch tensors on the device in and out, the
+observation vector decoded on the device, and no host wait.
 """
 from __future__ import annotations
 
@@ -22,6 +24,7 @@ from .runtime import Batch, _ptr
 
 # the learner's hyper-parameters do not enter the env (no epsilon draw, no Q-table access)
 ACTION_RESET = -2  # include/sfl.h SFL_ACTION_RESET: reset the env where it stands (env.reset() mid-episode)
+_STREAM_DEFAULT = 1  # include/sfl.h SFL_STREAM_DEFAULT: the device's default stream (its own handle is null)
 _ENV_HP = dict(gamma=1.0, epsilon=0.0, epsilon_decay_rate=1.0, lr=0.0, lr_decay_rate=1.0, default_q=0.0)
 
 
@@ -57,14 +60,92 @@ class AECBatch:
                       ("delays", C.c_int32), ("truncated", C.c_int32)):
             setattr(self._io, k, _ptr(self.out[k], ct))
         self._act = np.full(E, -1, np.int32)
+        self.device = device
+        self._t = None            # step_torch's tensors and descriptor (made by its first call)
+        self._stream = None       # the stream last handed to the library (step_torch on a HIP device)
+        self._host_stale = False  # device steps ran since the host arrays (self.out) were last filled
         self.lib.check(self.lib.dll.sfl_env_begin(self.batch.h), "sfl_env_begin")
 
     def close(self):
         self.batch.close()
 
+    # ---- the policy on the device: tensors in and out, no host in the loop -------------------------------
+    TORCH_FIELDS = FIELDS + ("arrived", "delays", "obs", "action_mask", "n_actions", "done")
+
+    def _torch_setup(self, torch):
+        E, T = self.E, self.cm.T
+        # the host build's "device" memory is host memory: the same path on CPU tensors
+        on_gpu = self.lib.device_count() > 0
+        dev = torch.device("cuda", self.device) if on_gpu else torch.device("cpu")
+        i32 = dict(dtype=torch.int32, device=dev)
+        out = {k: torch.zeros(E, **i32) for k in self.FIELDS}
+        out["arrived"] = torch.zeros((4, E), **i32)
+        out["delays"] = torch.zeros((T, E), **i32)
+        out["obs"] = torch.zeros((E, _lib.OBS_WIDTH), **i32)
+        out["action_mask"] = torch.zeros((E, _lib.MAX_ACTIONS), dtype=torch.uint8, device=dev)
+        out["n_actions"] = torch.zeros(E, **i32)
+        out["done"] = torch.zeros(E, dtype=torch.uint8, device=dev)
+        dio = _lib.EnvDevIO()
+        for k, ct in (("agent", C.c_int32), ("train", C.c_int32), ("slot", C.c_int32), ("state", C.c_uint32),
+                      ("mask", C.c_uint32), ("reward", C.c_int32), ("now", C.c_int32), ("next_switch", C.c_int32),
+                      ("step_now", C.c_int32), ("arrived", C.c_uint32), ("malfunctions", C.c_int32),
+                      ("delays", C.c_int32), ("truncated", C.c_int32)):
+            setattr(dio.io, k, C.cast(out[k].data_ptr(), _lib.P(ct)))
+        dio.obs = C.cast(out["obs"].data_ptr(), _lib.P(C.c_int32))
+        dio.action_mask = C.cast(out["action_mask"].data_ptr(), _lib.P(C.c_uint8))
+        dio.n_actions = C.cast(out["n_actions"].data_ptr(), _lib.P(C.c_int32))
+        dio.done = C.cast(out["done"].data_ptr(), _lib.P(C.c_uint8))
+        self._t = dict(out=out, dio=dio, dev=dev, on_gpu=on_gpu, none=torch.full((E,), -1, **i32), act=None)
+        return self._t
+
+    def step_torch(self, actions=None):
+        """``step`` for a policy that lives on the handle's device: ``actions`` is an int32 tensor [E] on that device
+        (None: no actions), the result a dict of tensors on it -- the ``FIELDS`` of ``step`` (all int32: ``state``,
+        ``mask`` and ``arrived`` hold the same bits as the uint32 host arrays), ``arrived`` [4, E], ``delays`` [T, E],
+        and the decoded decision: ``obs`` [E, 18] int32 (``observation(e)`` padded to four ports with -1),
+        ``action_mask`` [E, 16] uint8 (columns past ``n_actions`` are 0), ``n_actions`` [E] and ``done`` [E] uint8 (the episode ended in this call: the
+        row is -1, the mask 0, n_actions 0).  The tensors are allocated once and are views valid until the next
+        call.  The call is queued on torch's current stream and returns without waiting for the device.  There is
+        no range check on the host (the deciding agents are on the device): an action outside a switch's action
+        space is refused by the kernel, the same observation is emitted again, and ``sync()`` raises.  With the
+        host build (tests) the tensors are CPU tensors and the same path runs on the caller's thread."""
+        import torch
+        t = self._t or self._torch_setup(torch)
+        if actions is None:
+            a = t["none"]
+        else:
+            if not isinstance(actions, torch.Tensor) or actions.dtype != torch.int32:
+                raise ValueError("step_torch: actions must be an int32 tensor")
+            if tuple(actions.shape) != (self.E,) or not actions.is_contiguous():
+                raise ValueError(f"step_torch: actions of shape {tuple(actions.shape)} for {self.E} envs (contiguous [E])")
+            if actions.device != t["dev"]:
+                raise ValueError(f"step_torch: actions on {actions.device}, the envs are on {t['dev']}")
+            a = actions
+        if t["on_gpu"]:
+            # the library follows the stream the tensors are produced on (sfl_set_stream synchronises: only on a change)
+            s = torch.cuda.current_stream(t["dev"]).cuda_stream or _STREAM_DEFAULT
+            if s != self._stream:
+                self.lib.check(self.lib.dll.sfl_set_stream(self.batch.h, C.c_void_p(s)), "sfl_set_stream")
+                self._stream = s
+        t["act"] = a  # (alive until the next call: the kernel reads it after this call returned)
+        t["dio"].io.actions = C.cast(a.data_ptr(), _lib.P(C.c_int32))
+        self._host_stale = True
+        self.lib.check(self.lib.dll.sfl_env_step_dev(self.batch.h, C.byref(t["dio"])), "sfl_env_step_dev")
+        return t["out"]
+
+    def sync(self) -> None:
+        """Wait for the device steps queued so far; raises ``SflError`` if an env reported an error (a refused action)."""
+        self.lib.check(self.lib.dll.sfl_env_sync(self.batch.h), "sfl_env_sync")
+
     def step(self, actions: Optional[Sequence[int]] = None) -> Dict[str, np.ndarray]:
         """Apply ``actions[e]`` to each env's pending observation (None / < 0: none; ``ACTION_RESET``: reset the env
         where it stands) and run every env to its next observation or episode end.  Returns the output arrays (views, valid until the next call)."""
+        if self._host_stale:
+            # device steps (step_torch) ran since the host arrays were filled: a call without actions re-emits every
+            # env's pending observation into them (the range check below reads the deciding agents from there)
+            self._host_stale = False
+            self._io.actions = None
+            self.lib.check(self.lib.dll.sfl_env_step(self.batch.h, C.byref(self._io)), "sfl_env_step")
         if actions is None:
             self._act[:] = -1
         else:

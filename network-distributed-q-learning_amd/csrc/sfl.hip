@@ -42,6 +42,15 @@ __global__ void __launch_bounds__(256) k_run_ext(const sfl::SflMap* __restrict__
   if (e < s->E) sfl::env_run_ext<NW>(*m, *s, *c, e);
 }
 
+// device-resident external-action mode (sfl_env_step_dev), launched behind k_run_ext on the same stream: the dense
+// observation, action mask, action count and done flag of every env (sfl_core.h env_encode_item).  One thread per
+// 8-byte pair of obs[E][18]: a wavefront's 64 lanes store 512 contiguous bytes, the first E threads also their
+// row of the mask (16 bytes), n_actions and done.  No LDS, no scratch; the descriptor is a kernel argument.
+__global__ void __launch_bounds__(256) k_env_encode(const sfl::SflEnc x) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < x.E * (uint32_t)sfl::OBS_PAIRS) sfl::env_encode_item(x, t);
+}
+
 // One env per wavefront: k_wave / k_wave2; several envs per wavefront: k_wave_g (all in sfl_kwave_g.h).  Variant 7
 // of k_wave_g -- the bench's c3 shape -- is compiled in its own translation unit (sfl_kwave_v7.hip) with another
 // register-allocation-aware scheduler, and the kernels of handles with hyperparameter groups (HPG) in
@@ -525,6 +534,7 @@ struct HipBackend {
     if (ev1) hipEventDestroy(ev1);
     if (d_params) hipFree(d_params);
     if (d_pparams) hipFree(d_pparams);
+    if (d_eparams) hipFree(d_eparams);
     if (own_stream) hipStreamDestroy(own_stream);
   }
   // the host's waits for the device (stream / event synchronisations): sfl_get_sync_count
@@ -541,7 +551,8 @@ struct HipBackend {
   // null: back to the handle's own
   int set_stream(void* st) {
     if (!check(stream_wait(), "sync")) return -1;
-    stream = st ? (hipStream_t)st : own_stream;
+    // (SFL_STREAM_DEFAULT: the device's default stream, whose handle is the null pointer)
+    stream = st == SFL_STREAM_DEFAULT ? (hipStream_t) nullptr : st ? (hipStream_t)st : own_stream;
     return 0;
   }
   void* alloc(size_t bytes) {
@@ -558,6 +569,7 @@ struct HipBackend {
     check(stream_wait(), "d2h sync");
   }
   void memset(void* p, int v, size_t n) { check(hipMemsetAsync(p, v, n, stream), "memset"); }
+  void d2d(void* d, const void* s, size_t n) { check(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, stream), "d2d"); }
   // stream-ordered copy without the synchronisation (the caller syncs once for several)
   void d2h_async(void* d, const void* s, size_t n) { check(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, stream), "d2h"); }
   // time between the events of the last launch (after a sync)
@@ -709,6 +721,50 @@ struct HipBackend {
     float t = 0.f;
     hipEventElapsedTime(&t, ev0, ev1);
     *ms = t;
+    return err.empty() ? 0 : -1;
+  }
+  // sfl_env_step_dev: k_run_ext writing the caller's device buffers (x), then k_env_encode, queued without a
+  // wait.  The parameter block SflMap | SflState | SflCtl | SflExt has a device copy of its own, uploaded only
+  // when its contents change (as part_params): while the caller passes the same buffers, a call is two launches
+  // and no copy.
+  struct ExtParams {
+    sfl::SflMap m;
+    char p0[(sizeof(sfl::SflMap) + 63) / 64 * 64 - sizeof(sfl::SflMap)];
+    sfl::SflState s;
+    char p1[(sizeof(sfl::SflState) + 63) / 64 * 64 - sizeof(sfl::SflState)];
+    sfl::SflCtl c;
+    char p2[(sizeof(sfl::SflCtl) + 63) / 64 * 64 - sizeof(sfl::SflCtl)];
+    sfl::SflExt x;
+  };
+  void* d_eparams = nullptr;
+  ExtParams ep_host;
+  bool ep_valid = false;
+  int run_ext_dev(const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c, const sfl::SflExt& x,
+                  const sfl::SflEnc& enc) {
+    static_assert(sizeof(ExtParams) <= 4096, "params");
+    if (!d_eparams && !check(hipMalloc(&d_eparams, 4096), "hipMalloc params")) return -1;
+    auto* dp = (ExtParams*)d_eparams;
+    ExtParams hp;
+    ::memset(&hp, 0, sizeof hp);  // (padding included: the blocks are compared bytewise)
+    hp.m = m;
+    hp.s = s;
+    hp.c = c;
+    hp.c.ext = &dp->x;
+    hp.x = x;
+    if (!ep_valid || memcmp(&ep_host, &hp, sizeof hp) != 0) {
+      ep_host = hp;
+      ep_valid = true;
+      if (!check(hipMemcpyAsync(dp, &ep_host, sizeof hp, hipMemcpyHostToDevice, stream), "params h2d")) return -1;
+      if (!check(stream_wait(), "params sync")) return -1;
+    }
+    const unsigned blocks = (s.E + 63) / 64;  // (as run_ext)
+    if (m.T <= 32) k_run_ext<1><<<blocks, 64, 0, stream>>>(&dp->m, &dp->s, &dp->c);
+    else if (m.T <= 64) k_run_ext<2><<<blocks, 64, 0, stream>>>(&dp->m, &dp->s, &dp->c);
+    else k_run_ext<4><<<blocks, 64, 0, stream>>>(&dp->m, &dp->s, &dp->c);
+    if (!check(hipGetLastError(), "k_run_ext launch")) return -1;
+    const unsigned eblocks = (unsigned)(((size_t)enc.E * sfl::OBS_PAIRS + 255) / 256);
+    k_env_encode<<<eblocks, 256, 0, stream>>>(enc);
+    if (!check(hipGetLastError(), "k_env_encode launch")) return -1;
     return err.empty() ? 0 : -1;
   }
   int sync() { return check(stream_wait(), "sync") && err.empty() ? 0 : -1; }

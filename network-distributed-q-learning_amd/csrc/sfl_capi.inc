@@ -147,6 +147,21 @@ int sfl_env_step(sfl_handle* h, sfl_env_io* io) {
   return sfl::env_step(HH(h), io);
 }
 
+int sfl_env_step_dev(sfl_handle* h, const sfl_env_dev_io* io) {
+  if (!h) return sfl::fail("sfl_env_step_dev: null handle");
+  return sfl::env_step_dev(HH(h), io);
+}
+
+int sfl_env_sync(sfl_handle* h) {
+  if (!h) return sfl::fail("sfl_env_sync: null handle");
+  return sfl::env_sync(HH(h));
+}
+
+int sfl_get_obs_tables(sfl_handle* h, int32_t* switch_rc, int32_t* station_rc) {
+  if (!h) return sfl::fail("sfl_get_obs_tables: null handle");
+  return sfl::get_obs_tables(HH(h), switch_rc, station_rc);
+}
+
 int sfl_get_phase_cycles(sfl_handle* h, uint64_t* cycles, int32_t n) {
   if (!h || !cycles || n < 8) return sfl::fail("sfl_get_phase_cycles: null argument or n < 8");
   H* hh = HH(h);

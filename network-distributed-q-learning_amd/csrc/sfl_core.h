@@ -1509,4 +1509,97 @@ SFL_FN void env_run_ext(const SflMap& m, const SflState& s, const SflCtl& c, uin
   if (c.launch_bytes) c.launch_bytes[e] = 0;
 }
 
+// ---------------------------------------------------------------------------
+// device-resident external-action mode (sfl_env_step_dev): the dense observation of each env's pending decision
+// ---------------------------------------------------------------------------
+// After env_run_ext the per-env words (agent, slot, state, mask) are decoded into the reference's observation
+// vector [r, c, sem[P], target[2P], delay[P]] (observer.py:269-308; compiler.py obs_of_row) padded to four
+// ports -- obs[E][OBS_WIDTH], -1 in the columns of ports j >= P -- the action mask as bytes amask[E][MAX_ACTIONS],
+// the switch's action count n_actions[E] and done[E]; an env whose episode ended (agent == -1) gets an all -1
+// row, a zero mask, n_actions 0 and done 1.  The work is laid out by output address, not by env: item t writes
+// the 8-byte pair t of obs (an env's row is OBS_PAIRS = 9 pairs, which split at the vector's own fields: the
+// cell, sem[0..1], sem[2..3], target[0] .. target[3], delay[0..1], delay[2..3]), and the items t < E also
+// write row t of amask (one 16-byte store), n_actions[t] and done[t]: consecutive items write consecutive addresses of
+// every array.  The per-env words are read by the nine items of an env (one cache line serves seven envs)
+// and the two coordinate tables are a few hundred bytes.
+constexpr int OBS_WIDTH = 18, OBS_PAIRS = OBS_WIDTH / 2, MAX_ACTIONS = 16;
+struct SflEnc {
+  uint32_t E;
+  int32_t K;               // stations
+  const int32_t* agent;    // [E] the four words env_run_ext emitted
+  const int32_t* slot;     // [E]
+  const uint32_t* state;   // [E]
+  const uint32_t* mask;    // [E]
+  const uint8_t* sw_np;    // [S] ports
+  const uint8_t* sw_na;    // [S] actions incl. STOP
+  const int32_t* sw_rc;    // [S][2] switch cell (row, column)
+  const int32_t* st_rc;    // [K][2] station cell
+  int32_t* obs;            // [E][OBS_WIDTH] (8-byte aligned), or null
+  uint8_t* amask;          // [E][MAX_ACTIONS] (16-byte aligned), or null
+  int32_t* n_actions;      // [E] or null
+  uint8_t* done;           // [E] or null
+};
+struct alignas(8) ObsPair {
+  int32_t a, b;
+};
+struct alignas(16) MaskRow {
+  uint64_t lo, hi;
+};
+static_assert(MAX_ACTIONS == sizeof(MaskRow), "one 16-byte store per mask row");
+
+SFL_FN ObsPair obs_pair(const SflEnc& x, uint32_t e, uint32_t p) {
+  ObsPair o{-1, -1};
+  const int32_t sw = x.agent[e];
+  if (sw < 0) return o;
+  if (p == 0) {
+    o.a = x.sw_rc[2 * sw];
+    o.b = x.sw_rc[2 * sw + 1];
+    return o;
+  }
+  const int P = x.sw_np[sw], slot = x.slot[e];
+  const uint32_t st = x.state[e], K = (uint32_t)x.K;  // state = (free_bits * K + station) * 3 + delay level
+  if (p <= 2) {
+    const uint32_t bits = st / (3u * K);
+    const int j = 2 * ((int)p - 1);
+    if (j < P) o.a = (int32_t)((bits >> j) & 1u);
+    if (j + 1 < P) o.b = (int32_t)((bits >> (j + 1)) & 1u);
+  } else if (p <= 6) {
+    if ((int)p - 3 == slot) {
+      const uint32_t k = (st / 3u) % K;
+      o.a = x.st_rc[2 * k];
+      o.b = x.st_rc[2 * k + 1];
+    }
+  } else {
+    const int j = 2 * ((int)p - 7);
+    const int32_t lvl = (int32_t)(st % 3u);
+    if (j == slot) o.a = lvl;
+    if (j + 1 == slot) o.b = lvl;
+  }
+  return o;
+}
+
+// item t of OBS_PAIRS * E (see above)
+SFL_FN void env_encode_item(const SflEnc& x, uint32_t t) {
+  if (x.obs && t < x.E * (uint32_t)OBS_PAIRS) {
+    const uint32_t e = t / (uint32_t)OBS_PAIRS;
+    *(ObsPair*)(x.obs + 2 * (size_t)t) = obs_pair(x, e, t - e * (uint32_t)OBS_PAIRS);
+  }
+  if (t < x.E) {
+    const int32_t sw = x.agent[t];
+    const uint32_t na = sw < 0 ? 0u : x.sw_na[sw];
+    const uint32_t m = sw < 0 ? 0u : x.mask[t] & ((1u << na) - 1u);
+    if (x.amask) {
+      MaskRow w{0, 0};  // byte a = bit a of the mask
+#pragma unroll
+      for (int a = 0; a < 8; ++a) {
+        w.lo |= (uint64_t)((m >> a) & 1u) << (8 * a);
+        w.hi |= (uint64_t)((m >> (8 + a)) & 1u) << (8 * a);
+      }
+      *(MaskRow*)(x.amask + (size_t)MAX_ACTIONS * t) = w;
+    }
+    if (x.n_actions) x.n_actions[t] = (int32_t)na;
+    if (x.done) x.done[t] = sw < 0 ? 1 : 0;
+  }
+}
+
 }  // namespace sfl

@@ -66,6 +66,11 @@ struct Handle {
   SflExt ext{};
   SflExt* d_ext = nullptr;
   bool env_mode = false;
+  // the observation decode's coordinate tables (sfl_env_step_dev), derived at create: switch cells from cell_sw,
+  // station cells from tr_k / tr_target; max_na: the widest action space (the dense mask holds SFL_MAX_ACTIONS)
+  int32_t* d_sw_rc = nullptr;  // [S][2]
+  int32_t* d_st_rc = nullptr;  // [K][2]
+  int max_na = 0;
   // per-phase cycles of the sampled wavefronts, accumulated over learn / test launches on the device
   // (sfl_get_phase_cycles reads them)
   uint64_t* d_phase = nullptr;
@@ -287,6 +292,30 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
   m.tr_init_port = h->upload(md->tr_init_port, T);
   m.eps_tab = h->upload(hp->eps_tab, (size_t)hp->ntab);
   m.lr_tab = h->upload(hp->lr_tab, (size_t)hp->ntab);
+  {
+    // the observation vector's coordinates (observer.py:303-306: the switch cell, the target station's cell): the
+    // switch of a cell is cell_sw, every station is some train's target (compiler.py builds the stations from them)
+    std::vector<uint32_t> sw_rc(S * 2, 0xFFFFFFFFu), st_rc((size_t)md->K * 2, 0xFFFFFFFFu);
+    for (size_t cell = 0; cell < HW; ++cell) {
+      const int sw = md->cell_sw[cell];
+      if (sw >= 0 && (size_t)sw < S) {
+        sw_rc[2 * sw] = (uint32_t)(cell / (size_t)md->W);
+        sw_rc[2 * sw + 1] = (uint32_t)(cell % (size_t)md->W);
+      }
+    }
+    for (size_t t = 0; t < T; ++t) {
+      const int k = md->tr_k[t], cell = md->tr_target[t];
+      if (k >= 0 && k < md->K && cell >= 0) {
+        st_rc[2 * k] = (uint32_t)(cell / md->W);
+        st_rc[2 * k + 1] = (uint32_t)(cell % md->W);
+      }
+    }
+    for (size_t sw = 0; sw < S; ++sw) h->max_na = std::max(h->max_na, (int)md->sw_na[sw]);
+    h->keep.push_back(std::move(sw_rc));
+    h->d_sw_rc = (int32_t*)h->upload(h->keep.back().data(), S * 2);
+    h->keep.push_back(std::move(st_rc));
+    h->d_st_rc = (int32_t*)h->upload(h->keep.back().data(), (size_t)md->K * 2);
+  }
   {
     // packed tables for the one-env-per-wave kernel: one scalar load per switch / port / train,
     // and check_action as a table lookup
@@ -859,6 +888,84 @@ int env_step(Handle<B>* h, sfl_env_io* io) {
   get(io->truncated, x.truncated, E * 4);
   if (h->be.sync()) return fail(std::string("sfl_env_step: ") + h->be.error());
   return check_errors(h);
+}
+
+// sfl_env_step_dev: the same step with the caller's device buffers as the kernel's SflExt (a field the caller
+// leaves null goes to the handle's own buffer) and the dense observation decoded behind it (env_encode_item),
+// queued on the handle's stream without a wait; the envs' error flags stay in st.err for sfl_env_sync
+template <class B>
+int env_step_dev(Handle<B>* h, const sfl_env_dev_io* dio) {
+  if (!h->env_mode) return fail("sfl_env_step_dev: call sfl_env_begin first");
+  if (!dio) return fail("sfl_env_step_dev: null argument");
+  if (h->max_na > SFL_MAX_ACTIONS)
+    return fail("sfl_env_step_dev: the map has a switch with more than SFL_MAX_ACTIONS actions (the dense action mask "
+                "cannot hold it)");
+  if (((uintptr_t)dio->obs & 7u) || ((uintptr_t)dio->action_mask & 15u))
+    return fail("sfl_env_step_dev: obs must be 8-byte and action_mask 16-byte aligned");
+  if (h->E > 0xFFFFFFFFu / (uint32_t)OBS_PAIRS) return fail("sfl_env_step_dev: too many envs");
+  const sfl_env_io& io = dio->io;
+  const SflExt& own = h->ext;
+  SflExt x{};
+  // the actions go through the handle's own buffer (a stream-ordered device-to-device copy): a policy hands over a
+  // fresh tensor every call, and the kernel's parameter block stays the previous call's (no upload, no wait)
+  x.actions = own.actions;
+  if (io.actions) h->be.d2d((void*)own.actions, io.actions, (size_t)h->E * 4);
+  else h->be.memset((void*)own.actions, 0xFF, (size_t)h->E * 4);
+  x.agent = io.agent ? io.agent : own.agent;
+  x.train = io.train ? io.train : own.train;
+  x.slot = io.slot ? io.slot : own.slot;
+  x.state = io.state ? io.state : own.state;
+  x.mask = io.mask ? io.mask : own.mask;
+  x.reward = io.reward ? io.reward : own.reward;
+  x.now = io.now ? io.now : own.now;
+  x.next_sw = io.next_switch ? io.next_switch : own.next_sw;
+  x.step_now = io.step_now ? io.step_now : own.step_now;
+  x.arrived = io.arrived ? io.arrived : own.arrived;
+  x.n_mf = io.malfunctions ? io.malfunctions : own.n_mf;
+  x.delays = io.delays ? io.delays : own.delays;
+  x.truncated = io.truncated ? io.truncated : own.truncated;
+  SflEnc enc{};
+  enc.E = h->E;
+  enc.K = h->map.K;
+  enc.agent = x.agent;
+  enc.slot = x.slot;
+  enc.state = x.state;
+  enc.mask = x.mask;
+  enc.sw_np = h->map.sw_np;
+  enc.sw_na = h->map.sw_na;
+  enc.sw_rc = h->d_sw_rc;
+  enc.st_rc = h->d_st_rc;
+  enc.obs = dio->obs;
+  enc.amask = dio->action_mask;
+  enc.n_actions = dio->n_actions;
+  enc.done = dio->done;
+  SflCtl c{};
+  c.mode = 2;
+  c.launch_dec = h->d_launch_dec;
+  c.launch_ticks = h->d_launch_ticks;
+  c.launch_bytes = h->d_launch_bytes;
+  if (h->be.run_ext_dev(h->map, h->st, c, x, enc)) return fail(std::string("sfl_env_step_dev: ") + h->be.error());
+  return 0;
+}
+
+// sfl_env_sync: wait for the handle's stream and report the envs' error flags as sfl_env_step does (the
+// launch counters stay as the last host call left them)
+template <class B>
+int env_sync(Handle<B>* h) {
+  if (!h->env_mode) return fail("sfl_env_sync: call sfl_env_begin first");
+  uint64_t out[4] = {0, 0, 0, 0};
+  h->be.reduce_launch(h->d_launch_dec, h->d_launch_ticks, h->d_launch_bytes, h->st.err, h->E, h->d_sums);
+  h->be.d2h(out, h->d_sums, sizeof out);
+  if (h->be.sync()) return fail(std::string("sfl_env_sync: ") + h->be.error());
+  h->last_err = (uint32_t)out[3];
+  return scan_errors(h);
+}
+
+template <class B>
+int get_obs_tables(Handle<B>* h, int32_t* switch_rc, int32_t* station_rc) {
+  if (switch_rc) h->be.d2h(switch_rc, h->d_sw_rc, (size_t)h->map.S * 8);
+  if (station_rc) h->be.d2h(station_rc, h->d_st_rc, (size_t)h->map.K * 8);
+  return h->be.sync() ? fail(h->be.error()) : 0;
 }
 
 }  // namespace sfl

@@ -27,6 +27,7 @@ struct HostBackend {
   void h2d(void* d, const void* s, size_t n) { memcpy(d, s, n); }
   void d2h(void* d, const void* s, size_t n) { memcpy(d, s, n); }
   void d2h_async(void* d, const void* s, size_t n) { memcpy(d, s, n); }
+  void d2d(void* d, const void* s, size_t n) { memcpy(d, s, n); }
   float elapsed_ms() { return 0.f; }
   void memset(void* p, int v, size_t n) { ::memset(p, v, n); }
   void fill_f64(double* p, double v, size_t n) {
@@ -65,6 +66,18 @@ struct HostBackend {
       else sfl::env_run_ext<4>(m, s, c, (uint32_t)e);
     }
     *ms = 0.f;
+    return 0;
+  }
+  // sfl_env_step_dev: the env step into the caller's buffers ("device" memory is host memory here), then
+  // k_env_encode's items as a loop
+  int run_ext_dev(const sfl::SflMap& m, const sfl::SflState& s, sfl::SflCtl c, const sfl::SflExt& x,
+                  const sfl::SflEnc& enc) {
+    c.ext = &x;
+    float ms = 0.f;
+    run_ext(m, s, c, &ms);
+    const int64_t n = (int64_t)enc.E * sfl::OBS_PAIRS;
+#pragma omp parallel for
+    for (int64_t t = 0; t < n; ++t) sfl::env_encode_item(enc, (uint32_t)t);
     return 0;
   }
   int sync() { return 0; }

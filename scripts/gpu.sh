@@ -23,6 +23,8 @@
 #   rehearse   bench.py --gpus 2 / 4 (REH_N) as gloo ranks sharing this GPU: launcher, sharding, parity, the leg
 #   abenv      bench of the product library for each runtime setting in ABENV (e.g. "SFL_LDS_MAP=1 SFL_LDS_MAP=0")
 #   eval       the published evaluation table (scripts/eval_table.py) through libsfl.so, 15 trains
+#   aec        external-action mode's decision rate, policy on the host vs on the device (AEC_ARGS): profiles/aec_device_io.json
+#   aectrace   rocprofv3 --kernel-trace --stats of the device path alone at AEC_ENVS envs
 #   eval100    one 100-train learning run + greedy evaluation through libsfl.so (SEEDS100, default 66)
 set -o pipefail
 cd $GRAFT_REPO_ROOT
@@ -139,6 +141,13 @@ for S in "$@"; do
     eval100)  # one 100-train learning run (the two-slot k_wave shape) vs the host build's run of the same seed
       timeout -k 10 1000 python -u scripts/eval_table.py $OUT/eval100.json --trains 100 --size 100 --cities 25 --mf 0,0,0 --seeds ${SEEDS100:-66} --compare profiles/r06_100_trains_host.json > $OUT/eval100.log 2>&1; rc=$?
       grep -v "^\.\.\." $OUT/eval100.log | tail -6; ok $rc "eval100" ;;
+    aec)  # external-action mode, policy on the host vs on the device (scripts/aec_rate.py): profiles/aec_device_io.json
+      timeout -k 10 400 python -u scripts/aec_rate.py ${AEC_ARGS} > $OUT/aec_rate.log 2> $OUT/aec_rate.err; rc=$?
+      [ $rc -eq 0 ] || tail -5 $OUT/aec_rate.err; ok $rc "aec"
+      cp profiles/aec_device_io.json $OUT/; tail -1 $OUT/aec_rate.log ;;
+    aectrace)  # kernel trace of the device path alone (k_run_ext and k_env_encode against the gaps), AEC_ENVS envs
+      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/aec_prof -o ktrace --output-format csv -- python scripts/aec_rate.py --only device --rounds 1 --envs ${AEC_ENVS:-65536} --out $OUT/aec_trace_rate.json > $OUT/aec_trace.log 2>&1
+      ok $? "aectrace" ;;
     *)
       echo "unknown step $S"; exit 2 ;;
   esac
