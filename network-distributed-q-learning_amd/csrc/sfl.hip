@@ -18,9 +18,7 @@
 #include "sfl_kwave_g.h"
 #include "sfl_wave.h"
 
-SFL_KWAVE_V7(extern template)      // (defined in sfl_kwave_v7.hip)
-SFL_KWAVE_HPG(extern template)     // (hyperparameter groups: defined in sfl_kwave_hpg.hip)
-SFL_KWAVE_HPG_V7(extern template)  // (defined in sfl_kwave_hpg_v7.hip)
+SFL_KWAVE_UNIT(Main)  // this unit's wave kernels (sflk::owner: all but variant 7's and the HPG ones)
 
 namespace {
 
@@ -51,13 +49,8 @@ __global__ void __launch_bounds__(256) k_env_encode(const sfl::SflEnc x) {
   if (t < x.E * (uint32_t)sfl::OBS_PAIRS) sfl::env_encode_item(x, t);
 }
 
-// One env per wavefront: k_wave / k_wave2; several envs per wavefront: k_wave_g (all in sfl_kwave_g.h).  Variant 7
-// of k_wave_g -- the bench's c3 shape -- is compiled in its own translation unit (sfl_kwave_v7.hip) with another
-// register-allocation-aware scheduler, and the kernels of handles with hyperparameter groups (HPG) in
-// sfl_kwave_hpg.hip / sfl_kwave_hpg_v7.hip; this unit only declares those (below the includes).
-using sflk::k_wave;
-using sflk::k_wave2;
-using sflk::k_wave_g;
+// One env per wavefront: k_wave / k_wave2; several envs per wavefront: k_wave_g -- kernels and launch path in
+// sfl_kwave_g.h (sflk::launch), which also says which translation unit compiles which of them.
 
 // graph-partitioned rounds, local env step on the one-env-per-wave body (sfl_wave.h, PART)
 template <int PPL, int SPL, int TW>
@@ -74,6 +67,25 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SFL_WAV
 k_wave2_part(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict__ s, const sfl::SflCtl* __restrict__ c,
              const sfl::SflPart* __restrict__ P) {
   sfl::wave::run<PPL, SPL, TW, false, true>(*m, *s, *c, P);
+}
+
+// the partitioned local step of row V (the one-env-per-wave rows, G == 64), if the launch asks for it; true: launched
+template <int V>
+bool launch_part_row(int variant, uint32_t E, hipStream_t stream, const sfl::SflMap* m, const sfl::SflState* s,
+                     const sfl::SflCtl* c, const sfl::SflPart* P) {
+  constexpr sfl::WaveShape w = sfl::kVariants[V];
+  if constexpr (w.G == 64) {
+    if (variant != V) return false;
+    if constexpr (sflk::two_slot(w)) k_wave2_part<w.PPL, w.SPL, w.TW><<<sflk::grid_of(w, E), sflk::block_of(w), 0, stream>>>(m, s, c, P);
+    else k_wave_part<w.PPL, w.SPL, w.TW><<<sflk::grid_of(w, E), sflk::block_of(w), 0, stream>>>(m, s, c, P);
+    return true;
+  }
+  return false;
+}
+template <int... I>
+bool launch_part_wave(std::integer_sequence<int, I...>, int variant, uint32_t E, hipStream_t stream, const sfl::SflMap* m,
+                      const sfl::SflState* s, const sfl::SflCtl* c, const sfl::SflPart* P) {
+  return (launch_part_row<I + 1>(variant, E, stream, m, s, c, P) || ...);
 }
 
 // graph-partitioned rounds (sfl_part.h): local env step (lane per env), compaction into the
@@ -494,6 +506,25 @@ __global__ void k_qinit(sfl::SflMap m, sfl::SflState s, uint32_t n_rows, const u
   atomicOr(&s.touched[(size_t)e * m.touched_words + (rid >> 5)], 1u << (rid & 31u));
 }
 
+// A kernel's parameter structs in device memory: SflMap | SflState | SflCtl [| Tail], each at a 64-byte boundary
+// (they are passed by pointer, see k_run).  A host copy is zeroed with its padding, so two copies compare bytewise.
+struct ParamBlock3 {
+  alignas(64) sfl::SflMap m;
+  alignas(64) sfl::SflState s;
+  alignas(64) sfl::SflCtl c;
+};
+template <class Tail>
+struct ParamBlock : ParamBlock3 {
+  alignas(64) Tail t;
+};
+template <class B>
+void fill_params(B& b, const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c) {
+  ::memset((void*)&b, 0, sizeof b);
+  b.m = m;
+  b.s = s;
+  b.c = c;
+}
+
 struct HipBackend {
   static constexpr bool kHasWave = true;
   hipStream_t stream = nullptr;      // the stream every call of the handle queues on
@@ -589,95 +620,40 @@ struct HipBackend {
     k_qinit<<<blocks, 256, 0, stream>>>(m, s, n_rows, port, state, vals);
     check(hipGetLastError(), "k_qinit");
   }
-#ifdef SFL_PROFILE
-  // tuning builds: the wave kernels' phase cycles (sfl_wave.h g_prof), printed and cleared
-  void print_prof() {
-      unsigned long long pr[32] = {};
-      hipMemcpyFromSymbol(pr, HIP_SYMBOL(sfl::wave::g_prof), sizeof pr);
-      {  // variant 7's kernels count into their own translation unit's copy
-        unsigned long long p7[32] = {};
-        sflk::kwave_v7_prof_take(p7);
-        for (int k = 0; k < 32; ++k) pr[k] += p7[k];
-      }
-      fprintf(stderr,
-              "[sfl profile] cycles reset %.3e tick %.3e decide %.3e (observe %.3e egreedy %.3e apply %.3e) post %.3e "
-              "total %.3e | prefetch %llu row hit %llu miss %llu pend hit %llu miss %llu decisions %llu\n",
-              (double)pr[0], (double)pr[1], (double)pr[2], (double)pr[5], (double)pr[6], (double)pr[7], (double)pr[3],
-              (double)pr[4], pr[8], pr[9], pr[10], pr[11], pr[12], pr[13]);
-      fprintf(stderr, "[sfl laps]");
-      for (int k = 0; k < 16; ++k) fprintf(stderr, " %d:%.3e", k, (double)pr[16 + k]);
-      fprintf(stderr, "\n");
-      unsigned long long z[32] = {};
-      hipMemcpyToSymbol(HIP_SYMBOL(sfl::wave::g_prof), z, sizeof z);
-    }
-#endif
+  // run / run_ext: the block goes up with every call, queued in front of the launch (no wait)
+  const ParamBlock3* upload_params(const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c) {
+    static_assert(sizeof(ParamBlock3) <= 4096, "params");
+    ParamBlock3 hp;
+    fill_params(hp, m, s, c);
+    check(hipMemcpyAsync(d_params, &hp, sizeof hp, hipMemcpyHostToDevice, stream), "params h2d");
+    return (const ParamBlock3*)d_params;
+  }
+  // a block with a device copy of its own (run_ext_dev, part_params): `host` is what the device holds
+  template <class B>
+  bool push_params(B* dst, const B& host) {
+    return check(hipMemcpyAsync(dst, &host, sizeof host, hipMemcpyHostToDevice, stream), "params h2d");
+  }
+  // ... uploaded only when its bytes change, and then waited for: while they stay, a call pays no copy and no wait
+  template <class B>
+  bool sync_params(B* dst, B& host, bool& valid, const B& want) {
+    if (valid && memcmp(&host, &want, sizeof want) == 0) return true;
+    memcpy((void*)&host, &want, sizeof want);
+    valid = true;
+    return push_params(dst, host) && check(stream_wait(), "params sync");
+  }
   int run(const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c, int variant, float* ms) {
-    static_assert(sizeof(sfl::SflMap) + sizeof(sfl::SflState) + sizeof(sfl::SflCtl) + 64 < 4096, "params");
     const unsigned blocks = (s.E + 255) / 256;
-    char* base = (char*)d_params;
-    const size_t om = 0, os = (sizeof(sfl::SflMap) + 63) / 64 * 64,
-                 oc = os + (sizeof(sfl::SflState) + 63) / 64 * 64;
-    struct {
-      sfl::SflMap m;
-      char p0[(sizeof(sfl::SflMap) + 63) / 64 * 64 - sizeof(sfl::SflMap)];
-      sfl::SflState s;
-      char p1[(sizeof(sfl::SflState) + 63) / 64 * 64 - sizeof(sfl::SflState)];
-      sfl::SflCtl c;
-    } host_params;
-    host_params.m = m;
-    host_params.s = s;
-    host_params.c = c;
-    (void)om;
-    check(hipMemcpyAsync(d_params, &host_params, sizeof(host_params), hipMemcpyHostToDevice, stream), "params h2d");
+    const ParamBlock3* dp = upload_params(m, s, c);
+    const sfl::SflMap* pm = &dp->m;
+    const sfl::SflState* ps = &dp->s;
+    const sfl::SflCtl* pc = &dp->c;
     check(hipEventRecord(ev0, stream), "event");
-    const auto* pm = (const sfl::SflMap*)(base);
-    const auto* ps = (const sfl::SflState*)(base + os);
-    const auto* pc = (const sfl::SflCtl*)(base + oc);
-    const unsigned wblocks = (unsigned)(((size_t)s.E * 64 + SFL_WAVE_BLOCK - 1) / SFL_WAVE_BLOCK);
     // hyperparameter groups: the HPG instantiation, plain only (the engine refuses a trace and passes no phase
     // counters on a grouped handle); k_run reads the map's group pointer at run time
     const bool hpg = m.env_group != nullptr;
-#define SFL_KW(v)                                                                                                   \
-  {                                                                                                             \
-    constexpr sfl::WaveShape w = sfl::kVariants[v];                                                             \
-    if (hpg) k_wave<w.PPL, w.SPL, w.TW, false, false, true><<<wblocks, SFL_WAVE_BLOCK, 0, stream>>>(pm, ps, pc); \
-    else if (c.trace) k_wave<w.PPL, w.SPL, w.TW, true><<<wblocks, SFL_WAVE_BLOCK, 0, stream>>>(pm, ps, pc);     \
-    else if (c.phase_cyc) k_wave<w.PPL, w.SPL, w.TW, false, true><<<wblocks, SFL_WAVE_BLOCK, 0, stream>>>(pm, ps, pc); \
-    else k_wave<w.PPL, w.SPL, w.TW, false><<<wblocks, SFL_WAVE_BLOCK, 0, stream>>>(pm, ps, pc);                 \
-  }
-#define SFL_KW2(v)                                                                                       \
-  {                                                                                                             \
-    constexpr sfl::WaveShape w = sfl::kVariants[v];                                                             \
-    if (hpg) k_wave2<w.PPL, w.SPL, w.TW, false, false, true><<<s.E, 64, 0, stream>>>(pm, ps, pc);               \
-    else if (c.trace) k_wave2<w.PPL, w.SPL, w.TW, true><<<s.E, 64, 0, stream>>>(pm, ps, pc);                    \
-    else if (c.phase_cyc) k_wave2<w.PPL, w.SPL, w.TW, false, true><<<s.E, 64, 0, stream>>>(pm, ps, pc);         \
-    else k_wave2<w.PPL, w.SPL, w.TW, false><<<s.E, 64, 0, stream>>>(pm, ps, pc);                                \
-  }
-#define SFL_KG(v)                                                                                               \
-  {                                                                                                             \
-    constexpr sfl::WaveShape w = sfl::kVariants[v];                                                             \
-    const unsigned gblocks = (unsigned)(((size_t)s.E * w.G + SFL_GROUP_BLOCK - 1) / SFL_GROUP_BLOCK);             \
-    if (hpg) k_wave_g<w.PPL, w.SPL, w.TW, false, w.G, w.OCC, false, (bool)w.LM, true><<<gblocks, SFL_GROUP_BLOCK, 0, stream>>>(pm, ps, pc); \
-    else if (c.trace) k_wave_g<w.PPL, w.SPL, w.TW, true, w.G, w.OCC, false, (bool)w.LM><<<gblocks, SFL_GROUP_BLOCK, 0, stream>>>(pm, ps, pc); \
-    else if (c.phase_cyc)                                                                                       \
-      k_wave_g<w.PPL, w.SPL, w.TW, false, w.G, w.OCC, true, (bool)w.LM><<<gblocks, SFL_GROUP_BLOCK, 0, stream>>>(pm, ps, pc); \
-    else k_wave_g<w.PPL, w.SPL, w.TW, false, w.G, w.OCC, false, (bool)w.LM><<<gblocks, SFL_GROUP_BLOCK, 0, stream>>>(pm, ps, pc); \
-  }
-    static_assert(sfl::kVariants[5].TW > 64 && sfl::kNumVariants == 12, "variant 5 is the two-slot shape, 6-11 grouped");
-    if (variant == 1) SFL_KW(1)
-    else if (variant == 2) SFL_KW(2)
-    else if (variant == 3) SFL_KW(3)
-    else if (variant == 4) SFL_KW(4)
-    else if (variant == 5) SFL_KW2(5)
-    else if (variant == 6) SFL_KG(6)
-    else if (variant == 7) SFL_KG(7)
-    else if (variant == 8) SFL_KG(8)
-    else if (variant == 9) SFL_KG(9)
-    else if (variant == 10) SFL_KG(10)
-    else if (variant == 11) SFL_KG(11)
-#undef SFL_KG
-#undef SFL_KW2
-#undef SFL_KW
+    if (variant >= 1 && variant < sfl::kNumVariants)
+      sflk::launch({variant, hpg ? sflk::Mode::Hpg : c.trace ? sflk::Mode::Trace : c.phase_cyc ? sflk::Mode::Timed : sflk::Mode::Plain,
+                    s.E, stream, pm, ps, pc});
     else if (m.T <= 32) k_run<1><<<blocks, 256, 0, stream>>>(pm, ps, pc);
     else if (m.T <= 64) k_run<2><<<blocks, 256, 0, stream>>>(pm, ps, pc);
     else k_run<4><<<blocks, 256, 0, stream>>>(pm, ps, pc);
@@ -687,30 +663,15 @@ struct HipBackend {
     float t = 0.f;
     hipEventElapsedTime(&t, ev0, ev1);
     *ms = t;
-#ifdef SFL_PROFILE
-    if (variant > 0) print_prof();
-#endif
     return err.empty() ? 0 : -1;
   }
   // external-action mode: one call = every env applies its action and runs to its next observation
   int run_ext(const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c, float* ms) {
-    struct {
-      sfl::SflMap m;
-      char p0[(sizeof(sfl::SflMap) + 63) / 64 * 64 - sizeof(sfl::SflMap)];
-      sfl::SflState s;
-      char p1[(sizeof(sfl::SflState) + 63) / 64 * 64 - sizeof(sfl::SflState)];
-      sfl::SflCtl c;
-    } hp;
-    hp.m = m;
-    hp.s = s;
-    hp.c = c;
-    const size_t os = (sizeof(sfl::SflMap) + 63) / 64 * 64, oc = os + (sizeof(sfl::SflState) + 63) / 64 * 64;
-    char* base = (char*)d_params;
-    check(hipMemcpyAsync(d_params, &hp, sizeof(hp), hipMemcpyHostToDevice, stream), "params h2d");
+    const ParamBlock3* dp = upload_params(m, s, c);
+    const sfl::SflMap* pm = &dp->m;
+    const sfl::SflState* ps = &dp->s;
+    const sfl::SflCtl* pc = &dp->c;
     check(hipEventRecord(ev0, stream), "event");
-    const auto* pm = (const sfl::SflMap*)base;
-    const auto* ps = (const sfl::SflState*)(base + os);
-    const auto* pc = (const sfl::SflCtl*)(base + oc);
     const unsigned blocks = (s.E + 63) / 64;  // (64-thread blocks: few envs, spread over the CUs)
     if (m.T <= 32) k_run_ext<1><<<blocks, 64, 0, stream>>>(pm, ps, pc);
     else if (m.T <= 64) k_run_ext<2><<<blocks, 64, 0, stream>>>(pm, ps, pc);
@@ -727,15 +688,7 @@ struct HipBackend {
   // wait.  The parameter block SflMap | SflState | SflCtl | SflExt has a device copy of its own, uploaded only
   // when its contents change (as part_params): while the caller passes the same buffers, a call is two launches
   // and no copy.
-  struct ExtParams {
-    sfl::SflMap m;
-    char p0[(sizeof(sfl::SflMap) + 63) / 64 * 64 - sizeof(sfl::SflMap)];
-    sfl::SflState s;
-    char p1[(sizeof(sfl::SflState) + 63) / 64 * 64 - sizeof(sfl::SflState)];
-    sfl::SflCtl c;
-    char p2[(sizeof(sfl::SflCtl) + 63) / 64 * 64 - sizeof(sfl::SflCtl)];
-    sfl::SflExt x;
-  };
+  using ExtParams = ParamBlock<sfl::SflExt>;
   void* d_eparams = nullptr;
   ExtParams ep_host;
   bool ep_valid = false;
@@ -745,18 +698,10 @@ struct HipBackend {
     if (!d_eparams && !check(hipMalloc(&d_eparams, 4096), "hipMalloc params")) return -1;
     auto* dp = (ExtParams*)d_eparams;
     ExtParams hp;
-    ::memset(&hp, 0, sizeof hp);  // (padding included: the blocks are compared bytewise)
-    hp.m = m;
-    hp.s = s;
-    hp.c = c;
-    hp.c.ext = &dp->x;
-    hp.x = x;
-    if (!ep_valid || memcmp(&ep_host, &hp, sizeof hp) != 0) {
-      ep_host = hp;
-      ep_valid = true;
-      if (!check(hipMemcpyAsync(dp, &ep_host, sizeof hp, hipMemcpyHostToDevice, stream), "params h2d")) return -1;
-      if (!check(stream_wait(), "params sync")) return -1;
-    }
+    fill_params(hp, m, s, c);
+    hp.c.ext = &dp->t;
+    hp.t = x;
+    if (!sync_params(dp, ep_host, ep_valid, hp)) return -1;
     const unsigned blocks = (s.E + 63) / 64;  // (as run_ext)
     if (m.T <= 32) k_run_ext<1><<<blocks, 64, 0, stream>>>(&dp->m, &dp->s, &dp->c);
     else if (m.T <= 64) k_run_ext<2><<<blocks, 64, 0, stream>>>(&dp->m, &dp->s, &dp->c);
@@ -795,51 +740,34 @@ struct HipBackend {
     check(hipGetLastError(), "k_replicate");
   }
   // parameter block for the partitioned kernels: SflMap | SflState | SflCtl | SflPart
-  struct PartParams {
-    sfl::SflMap m;
-    char p0[(sizeof(sfl::SflMap) + 63) / 64 * 64 - sizeof(sfl::SflMap)];
-    sfl::SflState s;
-    char p1[(sizeof(sfl::SflState) + 63) / 64 * 64 - sizeof(sfl::SflState)];
-    sfl::SflCtl c;
-    char p2[(sizeof(sfl::SflCtl) + 63) / 64 * 64 - sizeof(sfl::SflCtl)];
-    sfl::SflPart P;
-  };
+  using PartParams = ParamBlock<sfl::SflPart>;
   // one device parameter block per round step (0 local, 1 owner; 2 unused), uploaded only when
   // its contents change: a round's steps reuse the same buffers, so after the first round no step
   // pays a host-to-device copy and its synchronisation
   void* d_pparams = nullptr;
   PartParams pp_host[3];
   bool pp_valid[3] = {false, false, false};
+  static constexpr size_t kPartStride = (sizeof(PartParams) + 255) / 256 * 256;
+  PartParams* part_slot(int which) const { return (PartParams*)((char*)d_pparams + which * kPartStride); }
   PartParams* part_params(int which, const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c,
                           const sfl::SflPart& P) {
-    static_assert(3 * ((sizeof(PartParams) + 255) / 256 * 256) <= 16384, "params");
-    constexpr size_t stride = (sizeof(PartParams) + 255) / 256 * 256;
+    static_assert(3 * kPartStride <= 16384, "params");
     if (!d_pparams && !check(hipMalloc(&d_pparams, 16384), "hipMalloc params")) return nullptr;
     PartParams hp;
-    ::memset(&hp, 0, sizeof hp);  // (the C library one, not this class's device memset) padding included: the blocks are compared bytewise
-    hp.m = m;
-    hp.s = s;
-    hp.c = c;
-    hp.P = P;
-    auto* dst = (PartParams*)((char*)d_pparams + which * stride);
-    if (pp_valid[which] && memcmp(&pp_host[which], &hp, sizeof hp) == 0) return dst;
-    pp_host[which] = hp;
-    pp_valid[which] = true;
-    check(hipMemcpyAsync(dst, &pp_host[which], sizeof hp, hipMemcpyHostToDevice, stream), "params h2d");
-    check(stream_wait(), "params sync");
-    return dst;
+    fill_params(hp, m, s, c);
+    hp.t = P;
+    sync_params(part_slot(which), pp_host[which], pp_valid[which], hp);
+    return part_slot(which);
   }
   // new segment capacities (sfl_part_set_caps, at a checkpoint): the uploaded parameter blocks take them now, so
   // the next rounds' launches find their blocks unchanged and upload nothing (no wait between checkpoints)
   void part_caps(const sfl::SflPart& P) {
     if (!d_pparams) return;
-    constexpr size_t stride = (sizeof(PartParams) + 255) / 256 * 256;
     bool any = false;
     for (int w = 0; w < 3; ++w) {
       if (!pp_valid[w]) continue;
-      pp_host[w].P.k_msg = P.k_msg;
-      check(hipMemcpyAsync((char*)d_pparams + w * stride, &pp_host[w], sizeof(PartParams), hipMemcpyHostToDevice, stream),
-            "params h2d");
+      pp_host[w].t.k_msg = P.k_msg;
+      push_params(part_slot(w), pp_host[w]);
       any = true;
     }
     if (any) check(stream_wait(), "params sync");
@@ -851,31 +779,20 @@ struct HipBackend {
     check(hipEventRecord(ev0, stream), "event");
     // one wave per block: a round's envs spread over as many CUs as possible
     const unsigned blocks = (s.E + 63) / 64;
-    const unsigned wblocks = (unsigned)(((size_t)s.E * 64 + SFL_WAVE_BLOCK - 1) / SFL_WAVE_BLOCK);
-#define SFL_KWP(v) \
-  k_wave_part<sfl::kVariants[v].PPL, sfl::kVariants[v].SPL, sfl::kVariants[v].TW><<<wblocks, SFL_WAVE_BLOCK, 0, stream>>>(&pp->m, &pp->s, &pp->c, &pp->P)
-    if (variant == 1) SFL_KWP(1);
-    else if (variant == 2) SFL_KWP(2);
-    else if (variant == 3) SFL_KWP(3);
-    else if (variant == 4) SFL_KWP(4);
-    else if (variant == 5)
-      k_wave2_part<sfl::kVariants[5].PPL, sfl::kVariants[5].SPL, sfl::kVariants[5].TW><<<s.E, 64, 0, stream>>>(&pp->m, &pp->s, &pp->c, &pp->P);
-#undef SFL_KWP
-    else if (m.T <= 32) k_part_local<1><<<blocks, 64, 0, stream>>>(&pp->m, &pp->s, &pp->c, &pp->P);
-    else if (m.T <= 64) k_part_local<2><<<blocks, 64, 0, stream>>>(&pp->m, &pp->s, &pp->c, &pp->P);
-    else k_part_local<4><<<blocks, 64, 0, stream>>>(&pp->m, &pp->s, &pp->c, &pp->P);
+    // the wave kernel of the handle's row (the G == 64 rows), else the lane-per-env body
+    if (launch_part_wave(std::make_integer_sequence<int, sfl::kNumVariants - 1>{}, variant, s.E, stream, &pp->m, &pp->s, &pp->c, &pp->t))
+      ;
+    else if (m.T <= 32) k_part_local<1><<<blocks, 64, 0, stream>>>(&pp->m, &pp->s, &pp->c, &pp->t);
+    else if (m.T <= 64) k_part_local<2><<<blocks, 64, 0, stream>>>(&pp->m, &pp->s, &pp->c, &pp->t);
+    else k_part_local<4><<<blocks, 64, 0, stream>>>(&pp->m, &pp->s, &pp->c, &pp->t);
     if (!check(hipGetLastError(), "k_part_local")) return -1;
     // (256 envs per block: fewer blocks reserve places and count themselves done; 64 measured -1.3 %)
-    k_part_compact<<<(s.E + SFL_COMPACT_BLOCK - 1) / SFL_COMPACT_BLOCK, SFL_COMPACT_BLOCK, 0, stream>>>(&pp->P, &pp->s, &pp->c,
+    k_part_compact<<<(s.E + SFL_COMPACT_BLOCK - 1) / SFL_COMPACT_BLOCK, SFL_COMPACT_BLOCK, 0, stream>>>(&pp->t, &pp->s, &pp->c,
                                                                                                   variant > 0 ? 0 : 1);
     check(hipEventRecord(ev1, stream), "event");
     // (no synchronisation here: the caller issues the launch totals and the count copies behind
     // it and syncs once; *ms is read with elapsed_ms() after that)
     *ms = 0.f;
-#ifdef SFL_PROFILE
-    if (!check(event_wait(ev1), "k_part_local")) return -1;
-    if (variant > 0) print_prof();
-#endif
     return err.empty() ? 0 : -1;
   }
   // the wave kernels' per-env scalar blocks from / into the SflState arrays (k_part_eblk)
@@ -891,7 +808,7 @@ struct HipBackend {
     if (!pp) return;
     const size_t units = (size_t)P.world * ((P.k_msg + OWN_CHUNK - 1) / OWN_CHUNK);
     const unsigned blocks = (unsigned)std::min<size_t>(units, 1024);
-    k_part_owner<<<blocks, OWN_CHUNK, 0, stream>>>(&pp->m, &pp->P, in, out);
+    k_part_owner<<<blocks, OWN_CHUNK, 0, stream>>>(&pp->m, &pp->t, in, out);
     check(hipGetLastError(), "k_part_owner");
   }
 };

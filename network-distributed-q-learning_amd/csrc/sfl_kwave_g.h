@@ -1,17 +1,19 @@
-// The wave kernels' __global__ wrappers, shared by the translation units that instantiate them.
+// The wave kernels' __global__ wrappers and their launch path, shared by the translation units that instantiate them.
 //
 // k_wave_g: several envs per wavefront (sfl_wave.h run_groups), G lanes per env, SFL_GROUP_BLOCK / G envs per
-// block: sfl.hip (every shape but variant 7) and sfl_kwave_v7.hip (variant 7, the bench's c3 shape, compiled with
-// the register-minimising scheduler).  k_wave / k_wave2: one env per wavefront (sfl_wave.h run): sfl.hip.
-// HPG = true (hyperparameter groups, sfl_set_hparam_groups): the plain instantiation of every shape, in
-// sfl_kwave_hpg.hip and -- variant 7, with variant 7's scheduler -- sfl_kwave_hpg_v7.hip, so that they compile in
-// parallel with sfl.hip; sfl.hip only declares them (extern template).
+// block.  k_wave / k_wave2: one env per wavefront (sfl_wave.h run).  Which unit compiles which kernel: owner()
+// below -- variant 7 (the bench's c3 shape) in sfl_kwave_v7.hip with the register-minimising scheduler, the
+// HPG = true kernels (hyperparameter groups, sfl_set_hparam_groups: the plain launch of every shape) in
+// sfl_kwave_hpg.hip and -- variant 7 -- sfl_kwave_hpg_v7.hip, so that they compile in parallel with sfl.hip, which
+// has all the others.
 //
 // Waves per SIMD the grouped kernel is register-budgeted for (sfl::kVariants[v].OCC): shapes with one train
 // slot per lane (TW <= G) 4 -- c2 (variant 6): 918 M vs 805 M at 3 (VGPR-bound, spills a little; 5: 589 M) --,
 // two slots per lane 4 with the prefetch ring (SFL_PF_RING: the LDS then allows 4 blocks per CU), 3 without it.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <utility>
 
 #include "sfl_engine.h"
 #include "sfl_wave.h"
@@ -49,53 +51,80 @@ k_wave_g(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict__ s,
   sfl::wave::run_groups<PPL, SPL, TW, TRACE, G, TIMED, LM, HPG>(*m, *s, *c);
 }
 
-// variant 7's three launches (traced, phase-timed, plain): explicit instantiation definitions in
-// sfl_kwave_v7.hip, declarations (extern template) in sfl.hip
-#define SFL_KWAVE_V7_ONE(PFX, TRACE, TIMED)                                                                        \
-  PFX __global__ void k_wave_g<sfl::kVariants[7].PPL, sfl::kVariants[7].SPL, sfl::kVariants[7].TW, TRACE,           \
-                               sfl::kVariants[7].G, sfl::kVariants[7].OCC, TIMED>(                                 \
-      const sfl::SflMap* __restrict__, const sfl::SflState* __restrict__, const sfl::SflCtl* __restrict__);
-#define SFL_KWAVE_V7(PFX)              \
-  namespace sflk {                     \
-  SFL_KWAVE_V7_ONE(PFX, true, false)   \
-  SFL_KWAVE_V7_ONE(PFX, false, true)   \
-  SFL_KWAVE_V7_ONE(PFX, false, false)  \
+// ---- one launch path from the shape table ---------------------------------------------------------------------
+// A cell = a row v of sfl::kVariants (1 .. kNumVariants - 1) x a launch mode.  Everything about a cell follows from
+// the row: its kernel family, its grid and block, and the translation unit that compiles it.
+static_assert(sizeof(sfl::kVariants) / sizeof(sfl::kVariants[0]) == sfl::kNumVariants, "kNumVariants counts kVariants' rows");
+enum class Mode { Plain, Trace, Timed, Hpg };  // Hpg: a handle with hyperparameter groups (plain only)
+// libsfl.so's translation units (build.TUS): sfl.hip, sfl_kwave_v7.hip, sfl_kwave_hpg.hip, sfl_kwave_hpg_v7.hip
+enum class Unit { Main, V7, Hpg, HpgV7 };
+constexpr int kSchedVariant = 7;  // the bench's c3 shape: its units are built with the register-minimising scheduler
+// the unit that owns a cell: it alone instantiates the cell's kernel, with its own compiler flags.  Every cell has
+// exactly one owner (this function's value); a unit that does not define its launch_unit fails the link.
+constexpr Unit owner(int v, Mode md) {
+  if (md == Mode::Hpg) return v == kSchedVariant ? Unit::HpgV7 : Unit::Hpg;
+  return v == kSchedVariant ? Unit::V7 : Unit::Main;
+}
+struct Launch {
+  int variant;
+  Mode mode;
+  uint32_t E;
+  hipStream_t stream;
+  const sfl::SflMap* m;
+  const sfl::SflState* s;
+  const sfl::SflCtl* c;
+};
+// grid and block of row w's kernels (the partitioned local step's too): k_wave packs SFL_WAVE_BLOCK / 64 envs into a
+// block, k_wave2 runs one env per 64-thread block, k_wave_g SFL_GROUP_BLOCK / G envs per block
+constexpr bool two_slot(const sfl::WaveShape& w) { return w.G == 64 && w.TW > 64; }
+constexpr unsigned block_of(const sfl::WaveShape& w) { return w.G < 64 ? SFL_GROUP_BLOCK : two_slot(w) ? 64 : SFL_WAVE_BLOCK; }
+constexpr unsigned grid_of(const sfl::WaveShape& w, uint32_t E) {
+  return two_slot(w) ? E : (unsigned)(((size_t)E * w.G + block_of(w) - 1) / block_of(w));
+}
+// launches cell (V, MD) if the launch asks for it and unit U owns it (only then is the kernel instantiated here)
+template <Unit U, int V, Mode MD>
+inline void launch_cell(const Launch& l) {
+  if constexpr (owner(V, MD) == U) {
+    constexpr sfl::WaveShape w = sfl::kVariants[V];
+    constexpr bool TRACE = MD == Mode::Trace, TIMED = MD == Mode::Timed, HPG = MD == Mode::Hpg;
+    if (l.variant != V || l.mode != MD) return;
+    if constexpr (w.G < 64)
+      k_wave_g<w.PPL, w.SPL, w.TW, TRACE, w.G, w.OCC, TIMED, (bool)w.LM, HPG><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
+    else if constexpr (two_slot(w))
+      k_wave2<w.PPL, w.SPL, w.TW, TRACE, TIMED, HPG><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
+    else
+      k_wave<w.PPL, w.SPL, w.TW, TRACE, TIMED, HPG><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
   }
-
-// the grouped-hyperparameter (HPG) launch of variant v, plain only: explicit instantiation definitions in
-// sfl_kwave_hpg.hip / sfl_kwave_hpg_v7.hip, declarations in sfl.hip
-#define SFL_KARGS const sfl::SflMap* __restrict__, const sfl::SflState* __restrict__, const sfl::SflCtl* __restrict__
-#define SFL_HPG_KW(PFX, v)                                                                                          \
-  PFX __global__ void k_wave<sfl::kVariants[v].PPL, sfl::kVariants[v].SPL, sfl::kVariants[v].TW, false, false, true>( \
-      SFL_KARGS);
-#define SFL_HPG_KW2(PFX, v)                                                                                          \
-  PFX __global__ void k_wave2<sfl::kVariants[v].PPL, sfl::kVariants[v].SPL, sfl::kVariants[v].TW, false, false, true>( \
-      SFL_KARGS);
-#define SFL_HPG_KG(PFX, v)                                                                                    \
-  PFX __global__ void k_wave_g<sfl::kVariants[v].PPL, sfl::kVariants[v].SPL, sfl::kVariants[v].TW, false,      \
-                               sfl::kVariants[v].G, sfl::kVariants[v].OCC, false, (bool)sfl::kVariants[v].LM, true>( \
-      SFL_KARGS);
-#define SFL_KWAVE_HPG(PFX) \
-  namespace sflk {         \
-  SFL_HPG_KW(PFX, 1)       \
-  SFL_HPG_KW(PFX, 2)       \
-  SFL_HPG_KW(PFX, 3)       \
-  SFL_HPG_KW(PFX, 4)       \
-  SFL_HPG_KW2(PFX, 5)      \
-  SFL_HPG_KG(PFX, 6)       \
-  SFL_HPG_KG(PFX, 8)       \
-  SFL_HPG_KG(PFX, 9)       \
-  SFL_HPG_KG(PFX, 10)      \
-  SFL_HPG_KG(PFX, 11)      \
+}
+template <Unit U, int... I>
+inline void launch_owned(const Launch& l, std::integer_sequence<int, I...>) {
+  ((launch_cell<U, I + 1, Mode::Plain>(l), launch_cell<U, I + 1, Mode::Trace>(l), launch_cell<U, I + 1, Mode::Timed>(l),
+    launch_cell<U, I + 1, Mode::Hpg>(l)), ...);
+}
+// a unit's launches: declared here, defined (SFL_KWAVE_UNIT) in the unit itself
+template <Unit U>
+void launch_unit(const Launch& l);
+template <>
+void launch_unit<Unit::Main>(const Launch& l);
+template <>
+void launch_unit<Unit::V7>(const Launch& l);
+template <>
+void launch_unit<Unit::Hpg>(const Launch& l);
+template <>
+void launch_unit<Unit::HpgV7>(const Launch& l);
+#define SFL_KWAVE_UNIT(U)                                                                           \
+  template <>                                                                                       \
+  void sflk::launch_unit<sflk::Unit::U>(const sflk::Launch& l) {                                    \
+    sflk::launch_owned<sflk::Unit::U>(l, std::make_integer_sequence<int, sfl::kNumVariants - 1>{}); \
   }
-#define SFL_KWAVE_HPG_V7(PFX) \
-  namespace sflk {            \
-  SFL_HPG_KG(PFX, 7)          \
+// the launch of a cell, from any unit: handed to its owner
+inline void launch(const Launch& l) {
+  switch (owner(l.variant, l.mode)) {
+    case Unit::Main: return launch_unit<Unit::Main>(l);
+    case Unit::V7: return launch_unit<Unit::V7>(l);
+    case Unit::Hpg: return launch_unit<Unit::Hpg>(l);
+    case Unit::HpgV7: return launch_unit<Unit::HpgV7>(l);
   }
-
-#ifdef SFL_PROFILE
-// (tuning builds) variant 7's phase cycles, read and cleared -- they count into sfl_kwave_v7.hip's own g_prof
-void kwave_v7_prof_take(unsigned long long* pr);
-#endif
+}
 
 }  // namespace sflk

@@ -3,6 +3,6 @@
 #include "sfl_kwave_g.h"
 
 namespace sflk {
-static_assert(sfl::kVariants[7].G == 16 && sfl::kVariants[7].TW == 32, "variant 7 is the c3 shape");
+static_assert(sfl::kVariants[kSchedVariant].G == 16 && sfl::kVariants[kSchedVariant].TW == 32, "variant 7 is the c3 shape");
 }
-SFL_KWAVE_HPG_V7(template)
+SFL_KWAVE_UNIT(HpgV7)

@@ -46,27 +46,6 @@ namespace wave {
 #ifndef SFL_TICK_REMMIN
 #define SFL_TICK_REMMIN 5  // ... and one of them has fewer than this many decisions left (0: hold regardless)
 #endif
-#ifdef SFL_PROFILE
-// tuning builds only: wall cycles per phase summed over waves (reset, tick, decide, post, total,
-// decide = observe + egreedy + apply)
-static __device__ unsigned long long g_prof[32];  // (one per translation unit: sfl_kwave_v7.hip has its own)
-#define SFL_PCNT(k) (prof[k] += 1)
-#define SFL_LAP0() (lap_t = (uint64_t)__builtin_amdgcn_s_memtime())
-#define SFL_LAP(k)                                                 \
-  do {                                                             \
-    const uint64_t _t = (uint64_t)__builtin_amdgcn_s_memtime();   \
-    lap[k] += _t - lap_t;                                          \
-    lap_t = _t;                                                    \
-  } while (0)
-#define SFL_PT(var) const uint64_t var = (uint64_t)__builtin_amdgcn_s_memtime()
-#define SFL_PACC(k, t0) prof[k] += (uint64_t)__builtin_amdgcn_s_memtime() - (t0)
-#else
-#define SFL_PT(var)
-#define SFL_PACC(k, t0)
-#define SFL_PCNT(k)
-#define SFL_LAP0()
-#define SFL_LAP(k)
-#endif
 
 // Wave priorities (s_setprio: the SIMD's issue arbiter prefers higher-priority waves): a wave in a tick above one
 // in a decision above one in its post step / bookkeeping.  Round 5 (profiles/r05ag_wave_priority_ab.txt): tick 2,
@@ -442,11 +421,6 @@ struct WEnv {
   // reads the stamps from a deciding lane after the (divergent) decide block
   bool tm_on = false;
   uint64_t tm_obs_t = 0, tm_eg_t = 0;
-#ifdef SFL_PROFILE
-  uint64_t prof[9] = {};  // decide: observe, epsilon-greedy, apply; events: prefetch, row hit/miss, pend hit/miss, decisions
-  uint64_t lap[16] = {};  // finer segments (see SFL_LAP call sites)
-  uint64_t lap_t = 0;
-#endif
 
   // lds: this env's region; ltt_shared: the block's copy of the timetable rows (G < 64), or null for
   // the env's own copy after its region
@@ -1212,7 +1186,6 @@ struct WEnv {
   //      flatland_lite.RailEnv.step), train-parallel: lane h = train h ----------------------------
   __device__ __forceinline__ void tick() {
     PrioGuard<PART ? 0 : SFL_SETPRIO_TICK> prio;  // (the partitioned local step: no gain, profiles/r05ag_*)
-    SFL_LAP0();
     if constexpr (xp::kNoTick) {
       ++now;
       return;
@@ -1316,7 +1289,6 @@ struct WEnv {
         bits[k] = tb_make(dir, st_, prev, saved, mf, tb_done(b));
       }
     }
-    SFL_LAP(11);
     // pass 2: motion check, least fixed point (flatland_lite.motion_check): the lowest handle
     // wanting a cell wins it; a cell can be entered if free or its occupant moves out
     const Mask M = mbal(mover);
@@ -1385,7 +1357,6 @@ struct WEnv {
         A |= nb;
       }
     }
-    SFL_LAP(12);
     // pass 3: state machine + positions, deviation fix
     const bool over = t >= m.max_episode_steps;
     bool done[TPL], isdone[TPL], newly[TPL], dep[TPL];
@@ -1456,7 +1427,6 @@ struct WEnv {
       }
     }
     arr_mask |= mbal(newly);
-    SFL_LAP(13);
     // delete the semaphores of done trains (switch_env.py:370-376): each lane its own records
     const Mask DONE = mbal(done);
     if (many(DONE)) {
@@ -1503,7 +1473,6 @@ struct WEnv {
     const Mask MF = mbal(mfp);
     n_mf += mpopc(MF & ~mf_mask);
     mf_mask = MF;
-    SFL_LAP(14);
     // _check_active_switch (switch_env.py:427-485)
     // (the slots' move-table loads issued together)
     int sw_next[TPL];  // the switch at the cell the train's next rail action leads to (-1: none)
@@ -1538,7 +1507,6 @@ struct WEnv {
       }
     }
     q_mask = mbal(act);
-    SFL_LAP(15);
     const Mask full = mfirst(Mask{}, m.T);
     const Mask ALL = mbal(isdone);
     ep_ticks += 1;
@@ -1776,20 +1744,20 @@ struct WEnv {
 
   // ---- decision (wave-uniform): observe (observer.py:246-308), epsilon-greedy
   //      (distr_q.py:312-319), _apply_action (switch_env.py:203-294) ---------------------------
-  struct Dec {
-    int sw, h, slot;
-    uint32_t state;
-    int action, j;
-    int32_t reward, r_new;
-    int next_sw;
-    uint64_t slotword;
-    double mq;        // max over the full decision row (successor value for the pending update)
-    uint32_t qoff_pend;  // Q cell (offset in the env's block) of the pending update consumed here, or PF_NONE
-    double q_pend;    // its value, loaded during the decision
-    uint32_t row_pend;  // key-set row of the pending update
-    uint32_t row_cur;   // key-set row of this decision's observation
-    bool touch_cur;     // greedy choice: insert row_cur into the key set (max_action's __check_entry)
-    uint32_t abytes;    // algorithmic bytes of the decision
+  struct Dec {  // (a driver starts from the zero record: no decision in flight)
+    int sw = 0, h = 0, slot = 0;
+    uint32_t state = 0;
+    int action = 0, j = 0;
+    int32_t reward = 0, r_new = 0;
+    int next_sw = 0;
+    uint64_t slotword = 0;
+    double mq = 0.0;        // max over the full decision row (successor value for the pending update)
+    uint32_t qoff_pend = PF_NONE;  // Q cell (offset in the env's block) of the pending update consumed here, or PF_NONE
+    double q_pend = 0.0;    // its value, loaded during the decision
+    uint32_t row_pend = 0;  // key-set row of the pending update
+    uint32_t row_cur = 0;   // key-set row of this decision's observation
+    bool touch_cur = false;     // greedy choice: insert row_cur into the key set (max_action's __check_entry)
+    uint32_t abytes = 0;    // algorithmic bytes of the decision
   };
 
   // PART: true = observe pass (no reply yet): the request went to the row's owner and nothing of
@@ -1801,8 +1769,6 @@ struct WEnv {
     // PART: a row of this rank's own switches is decided in one pass, like the fused kernel
     const bool loc = local_sw((int)(trl(sdec, mctz(q_mask)) >> 16));
     const bool observe_only = PART && !(flags & F_REQ) && !loc;
-    SFL_PT(t_obs);
-    SFL_LAP0();
     // agent_iter: lowest queued train (switch_env.py:418-421, 616-622)
     // (PART observe pass: the observation needs one distance, looked up directly below; the
     // staging waits for the apply pass in the next launch)
@@ -1812,10 +1778,7 @@ struct WEnv {
     if ((!pf_ok || (RING && pf_n >= PF_SLOTS)) && !observe_only) {
       prefetch(greedy);
       pf_ok = !PART;  // (PART stages only this decision's train: the next one stages its own)
-      SFL_PCNT(3);
     }
-    SFL_LAP(0);
-    SFL_PCNT(8);
     const int h = mctz(q_mask);
     if (!observe_only) mclear_low(q_mask);
     const uint32_t sd = trl(sdec, h);
@@ -1850,7 +1813,6 @@ struct WEnv {
       lerr |= E_PORT;
       slot = 0;
     }
-    SFL_LAP(1);
     // observe: lane j < np evaluates check_port_blocked(next_port(p_j), p_j) for port j of the
     // switch (observer.py:44-151, 269-283), branch-free integer VALU, then one ballot; lane a
     // evaluates get_action_mask for route a (switch_agents.py:104-134)
@@ -1863,7 +1825,6 @@ struct WEnv {
     const uint32_t rn = lsem[nbj], ro = lsem[pj];
     const uint32_t blk = rec_blocks(rn, (uint32_t)h, malf, 0u) | rec_blocks(ro, (uint32_t)h, malf, 1u);
     const uint32_t free_bits = (uint32_t)BAL(pvalid && blk == 0u) & 15u;
-    SFL_LAP(2);
     const uint32_t b = trl(bits, h);
     const int32_t p0 = trl(pos, h);
     const int32_t ed = tr[0], la = tr[1], k = tr[2];
@@ -1877,12 +1838,9 @@ struct WEnv {
     const uint32_t amask =
         ((uint32_t)BAL(lid() < na - 1 && srca == (uint32_t)slot && ((free_bits >> dsta) & 1u)) & 0xFFu) |
         (1u << (na - 1));
-    SFL_LAP(3);
     if constexpr (TM) {  // observe done (observer.py:246-308)
       if (tm_on) tm_obs_t = (uint64_t)__builtin_amdgcn_s_memtime();
     }
-    SFL_PACC(0, t_obs);
-    SFL_PT(t_eg);
     // issue the Q row load and the pending update's Q cell load, then draw while they fly
     const PortRec prr = port_rec(4 * sw + slot);
     const int w = prr.q_w();
@@ -1892,13 +1850,7 @@ struct WEnv {
     const bool colv = lid() < w;
     const bool row_hit = pf_roff_h == roff;  // the staged row and its greedy choice are valid
     double v_c = 0.0;
-    if (row_hit) {
-      SFL_PCNT(4);
-    } else if (loc) {
-      v_c = ld(qbase() + roff, (size_t)(colv ? lid() : 0));
-      SFL_PCNT(5);
-    }
-    SFL_LAP(4);
+    if (!row_hit && loc) v_c = ld(qbase() + roff, (size_t)(colv ? lid() : 0));
     d.slotword = U(slot_v);
     const uint32_t pend = greedy ? PEND_NONE : slot_pend(d.slotword, epoch);
     d.qoff_pend = PF_NONE;
@@ -1918,14 +1870,11 @@ struct WEnv {
         // the pending update is applied by its row's owner (PART: d.qoff_pend stays PF_NONE; post_part emits the record)
       } else if (pf_qoff_h == d.qoff_pend) {
         q_pend_v = pf_qp;
-        SFL_PCNT(6);
       } else {
         q_pend_v = ld(qbase(), (size_t)d.qoff_pend);
-        SFL_PCNT(7);
       }
     }
     const int32_t reward = slot_rew(d.slotword, epoch);
-    SFL_LAP(5);
     // epsilon-greedy
     int action = -1;
     bool explore = false;
@@ -1997,7 +1946,6 @@ struct WEnv {
       }
       flags &= ~F_REQ;
     }
-    SFL_LAP(6);
     d.q_pend = Ud(q_pend_v);
     // np.argmax over the full row (first maximum), max(row), and the first allowed maximum
     // (distr_q.py:449-490), over the compact columns held by lanes 0..w-1 (column order = action
@@ -2042,12 +1990,9 @@ struct WEnv {
     // so the apply below branches on the scalar unit instead of through exec-mask regions
     action = U(action);
     if (action < 0 || action >= na) lerr |= E_BAD_ACTION;
-    SFL_LAP(7);
     if constexpr (TM) {  // action selected (distr_q.py:312-319)
       if (tm_on) tm_eg_t = (uint64_t)__builtin_amdgcn_s_memtime();
     }
-    SFL_PACC(1, t_eg);
-    SFL_PT(t_ap);
     // _apply_action
     const int stop = na - 1;
     bool moving = false;
@@ -2099,7 +2044,6 @@ struct WEnv {
       q4.store();
       // check_port_blocked(target, out_p) on the updated records (reward_func.py:62-70)
       blk_moving = (rec_blocks(q4.v[1], (uint32_t)h, malf, 0u) | rec_blocks(q4.v[0], (uint32_t)h, malf, 1u)) != 0u;
-      SFL_LAP(8);
       tset(sdec, h, (sd & 0xFFFF0000u) | (uint32_t)in_p);
       tset(nprv, h, (uint32_t)target | ((uint32_t)out_p << 16));
       next_sw = target >> 2;
@@ -2141,8 +2085,6 @@ struct WEnv {
     d.reward = reward;
     d.next_sw = next_sw;
     d.abytes = 220u + 48u * (uint32_t)np + 8u * (uint32_t)na;  // SURVEY.md §8(d) bytes of this decision
-    SFL_LAP(9);
-    SFL_PACC(2, t_ap);
     return false;
   }
 
@@ -2192,7 +2134,6 @@ struct WEnv {
       post_part(d, greedy);
       return;
     }
-    SFL_LAP0();
     if (greedy) {
       if (lid() == 0) {
         if (d.touch_cur) touch_row(d.row_cur);
@@ -2268,7 +2209,6 @@ struct WEnv {
       }
     }
     cset(d.sw, cget(d.sw) + 1u);
-    SFL_LAP(10);
   }
   // PART: post with the Q operations on other ranks' rows as update records to their owners (env_post
   // with MsgQ in sfl_part.h; stage stg = the pending update and key-set insert, then one stage per
@@ -2374,6 +2314,57 @@ struct WEnv {
     for (int off = 1; off < G; off <<= 1) c0 += (uint64_t)__shfl_xor((long long)c0, off, 64);
     return c0;
   }
+
+  // ---- bookkeeping shared by the drivers (run / run_groups), which keep their loop shapes, their timer laps and
+  //      their own types of the launch bounds.  `ln`: the driver's own copy of the lane in the env's group.
+  //      The greedy choice at PH_RESET and the PH_END block stay written out in both drivers: as helpers they are
+  //      simplified on their own before they are inlined, and every kernel then allocates its registers
+  //      differently (other spill counts) -------------------------------------------------------------------
+  // the phase after a tick: the episode's end or the queued decisions, behind the post of a decision in flight
+  __device__ __forceinline__ int32_t after_tick() const {
+    if (flags & F_TERM) return (flags & F_INFLIGHT) ? PH_POST : PH_END;
+    if (many(q_mask)) return (flags & F_INFLIGHT) ? PH_POST : PH_DECIDE;
+    return PH_TICK;
+  }
+  // the traced env's record of a posted decision (TRACE instantiations; the driver asks whether this env is the one)
+  __device__ __forceinline__ void trace_decision(const SflCtl& c, const Dec& d, int ln) {
+    const uint64_t cs = sem_checksum();
+    if (ln == 0) {
+      const uint64_t n = *c.trace_n;
+      if (n < (uint64_t)c.trace_cap) {
+        uint64_t* tp = c.trace + 4 * n;
+        tp[0] = (uint64_t)(uint32_t)now | ((uint64_t)(uint32_t)d.sw << 16) | ((uint64_t)(uint32_t)d.h << 32) |
+                ((uint64_t)(uint32_t)d.action << 48);
+        tp[1] = (uint64_t)d.state | ((uint64_t)(uint32_t)d.reward << 32);
+        tp[2] = cs;
+        tp[3] = (uint64_t)(uint32_t)d.next_sw;
+      }
+      *c.trace_n = n + 1;
+    }
+  }
+  // loop bookkeeping of a posted decision; max_steps in the driver's own width
+  template <class Steps>
+  __device__ __forceinline__ void count_decision(const Dec& d, Steps max_steps) {
+    flags &= ~F_INFLIGHT;
+    cum += d.reward;
+    ep_dec += 1;
+    n_dec += 1;
+    step_ctr += 1;
+    if (step_ctr > max_steps) flags |= F_TRUNC;
+  }
+  // the phase after a post: the episode's end, or the next queued decision
+  __device__ __forceinline__ int32_t after_post() const { return (flags & (F_TERM | F_TRUNC)) ? PH_END : PH_DECIDE; }
+  // after the loop: the episode counters and the launch's totals (the partitioned step keeps them in the env's
+  // scalar block instead: store_eblk)
+  __device__ __forceinline__ void store_launch(const SflCtl& c, int32_t ep_t, int32_t n_test, uint32_t ticks,
+                                               uint32_t abytes, int ln) {
+    if (ln != 0) return;
+    st(s.ep_t, e, ep_t);
+    st(s.n_test, e, n_test);
+    if (c.launch_dec) st(c.launch_dec, e, (uint64_t)n_dec);
+    if (c.launch_ticks) st(c.launch_ticks, e, (uint64_t)ticks);
+    if (c.launch_bytes) st(c.launch_bytes, e, (uint64_t)abytes);
+  }
 };
 
 // driver: one env per wavefront until its episode target / decision budget (env_run in sfl_core.h)
@@ -2466,21 +2457,8 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
   int32_t n_test = PART ? (int32_t)v.ebw(EB_N_TEST) : uni(ld(s.n_test, e));
   uint32_t ticks = 0, abytes = 0;
   typename V::Dec d;
-  d.sw = d.h = d.slot = d.action = d.j = d.reward = d.r_new = d.next_sw = 0;
-  d.state = 0;
-  d.slotword = 0;
-  d.mq = d.q_pend = 0.0;
-  d.qoff_pend = PF_NONE;
-  d.row_pend = 0;
-  d.row_cur = 0;
-  d.touch_cur = false;
-  d.abytes = 0;
   const bool test_mode = c.mode == 1;
   const int64_t max_steps = m.max_steps, dec_budget = c.dec_budget;
-#ifdef SFL_PROFILE
-  uint64_t prof[5] = {0, 0, 0, 0, 0};
-  const uint64_t t_begin = (uint64_t)__builtin_amdgcn_s_memtime();
-#endif
   while (true) {
     if (phase == PH_RESET) {
       // learn: optional greedy round before episode t (distr_q.py:278-281)
@@ -2492,53 +2470,27 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
         if (c.exploit_freq > 0 && (ep_t + 1) % c.exploit_freq == 0 && !(v.flags & F_EXPLOIT_DONE)) v.flags |= F_GREEDY;
         else v.flags &= ~F_GREEDY;
       }
-      SFL_PT(t0);
       if constexpr (TIMED) tm.lap(TM_OTHER);
       v.reset();
       if constexpr (TIMED) tm.lap(TM_RESET);
-      SFL_PACC(0, t0);
       phase = PH_TICK;
     } else if (phase == PH_TICK) {
       abytes += 36u * (uint32_t)(m.T - mpopc(v.arr_mask));
-      SFL_PT(t0);
       if constexpr (TIMED) tm.lap(TM_OTHER);
       v.tick();
       if constexpr (TIMED) tm.lap(TM_TICK);
-      SFL_PACC(1, t0);
       ticks++;
-      if (v.flags & F_TERM) phase = (v.flags & F_INFLIGHT) ? PH_POST : PH_END;
-      else if (many(v.q_mask)) phase = (v.flags & F_INFLIGHT) ? PH_POST : PH_DECIDE;
+      phase = v.after_tick();
     } else if (phase == PH_DECIDE || phase == PH_POST) {
       const bool greedy = (v.flags & F_GREEDY) != 0;
       // post step + loop bookkeeping of decision d; true: the launch's decision budget is spent
       auto finish = [&]() -> bool {
-        SFL_PT(t0);
         if constexpr (TIMED) tm.lap(TM_OTHER);
         v.post(d, greedy);
         if constexpr (TIMED) tm.lap(TM_POST);
-        SFL_PACC(3, t0);
-        if (TRACE && c.trace && (int32_t)e == c.trace_env) {
-          const uint64_t cs = v.sem_checksum();
-          if (lane == 0) {
-            const uint64_t n = *c.trace_n;
-            if (n < (uint64_t)c.trace_cap) {
-              uint64_t* tp = c.trace + 4 * n;
-              tp[0] = (uint64_t)(uint32_t)v.now | ((uint64_t)(uint32_t)d.sw << 16) | ((uint64_t)(uint32_t)d.h << 32) |
-                      ((uint64_t)(uint32_t)d.action << 48);
-              tp[1] = (uint64_t)d.state | ((uint64_t)(uint32_t)d.reward << 32);
-              tp[2] = cs;
-              tp[3] = (uint64_t)(uint32_t)d.next_sw;
-            }
-            *c.trace_n = n + 1;
-          }
-        }
-        v.flags &= ~F_INFLIGHT;
-        v.cum += d.reward;
-        v.ep_dec += 1;
-        v.n_dec += 1;
-        v.step_ctr += 1;
-        if (v.step_ctr > max_steps) v.flags |= F_TRUNC;
-        phase = (v.flags & (F_TERM | F_TRUNC)) ? PH_END : PH_DECIDE;
+        if (TRACE && c.trace && (int32_t)e == c.trace_env) v.trace_decision(c, d, lane);
+        v.count_decision(d, max_steps);
+        phase = v.after_post();
         return dec_budget > 0 && dec_base + (int64_t)v.n_dec >= dec_budget;
       };
       // a batch of queued decisions: decide, and post each one while more are queued (the last
@@ -2551,14 +2503,12 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
             stop = true;  // this part step's decisions are done: no new request
             break;
           }
-          SFL_PT(t0);
           if constexpr (TIMED) {
             tm.lap(TM_OTHER);
             v.tm_on = tm.on;
           }
           const bool requested = v.template decide<TIMED>(d, greedy);
           if constexpr (TIMED) tm.decide_done(v, 0);
-          SFL_PACC(2, t0);
           if (PART && requested) {
             stop = true;  // the round ends at the request (phase stays PH_DECIDE)
             break;
@@ -2614,21 +2564,7 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
     v.store_eblk(phase, err_out, ep_t, n_test, dec_base + (int64_t)v.n_dec, v.req_dst_v,
                  v.n_upd < P->upd_env ? v.n_upd : P->upd_env, (uint64_t)v.n_dec, (uint64_t)ticks, (uint64_t)abytes);
   if constexpr (TIMED) tm.flush(c);
-#ifdef SFL_PROFILE
-  prof[4] = (uint64_t)__builtin_amdgcn_s_memtime() - t_begin;
-  if (lane == 0) {
-    for (int k = 0; k < 5; ++k) atomicAdd(&g_prof[k], (unsigned long long)prof[k]);
-    for (int k = 0; k < 9; ++k) atomicAdd(&g_prof[5 + k], (unsigned long long)v.prof[k]);
-    for (int k = 0; k < 16; ++k) atomicAdd(&g_prof[16 + k], (unsigned long long)v.lap[k]);
-  }
-#endif
-  if (lane == 0 && !PART) {
-    st(s.ep_t, e, ep_t);
-    st(s.n_test, e, n_test);
-    if (c.launch_dec) st(c.launch_dec, e, (uint64_t)v.n_dec);
-    if (c.launch_ticks) st(c.launch_ticks, e, (uint64_t)ticks);
-    if (c.launch_bytes) st(c.launch_bytes, e, (uint64_t)abytes);
-  }
+  if constexpr (!PART) v.store_launch(c, ep_t, n_test, ticks, abytes, lane);
 }
 
 // driver for G < 64 (several envs per wavefront, one per lane group): the same per-env sequence
@@ -2683,38 +2619,13 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
   int32_t ep_t = ld(s.ep_t, e), n_test = ld(s.n_test, e);
   uint32_t ticks = 0, abytes = 0;
   typename V::Dec d;
-  d.sw = d.h = d.slot = d.action = d.j = d.reward = d.r_new = d.next_sw = 0;
-  d.state = 0;
-  d.slotword = 0;
-  d.mq = d.q_pend = 0.0;
-  d.qoff_pend = PF_NONE;
-  d.row_pend = 0;
-  d.row_cur = 0;
-  d.touch_cur = false;
-  d.abytes = 0;
   const bool test_mode = c.mode == 1;
   // 32-bit bounds (step_ctr and n_dec are 32-bit counters): held as two 64-bit values across the
   // loop they were spilled, and the decision count reloaded from scratch every post (c3: 1,356 M ->
   // 1,404 M agent-env-steps/s)
   const int32_t max_steps = m.max_steps < 0x7FFFFFFF ? (int32_t)m.max_steps : 0x7FFFFFFF;
   const uint32_t dec_budget = c.dec_budget > 0 ? (c.dec_budget < 0xFFFFFFFFll ? (uint32_t)c.dec_budget : 0xFFFFFFFFu) : 0xFFFFFFFFu;
-#ifdef SFL_PROFILE
-  // group activity of the flat loop (per wave, lane 0): iterations, and per iteration the groups
-  // that tick / post / decide, and the iterations with any tick
-  uint64_t gs[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // + wall cycles of the tick / post / decide blocks
-  uint64_t tp0 = 0;
-#endif
   while (true) {
-#ifdef SFL_PROFILE
-    {
-      const uint64_t bt = __ballot(phase == PH_TICK), bp = __ballot(phase == PH_POST), bd = __ballot(phase == PH_DECIDE);
-      gs[0] += 1;
-      gs[1] += (uint64_t)__builtin_popcountll(bt) / G;
-      gs[2] += (uint64_t)__builtin_popcountll(bp) / G;
-      gs[3] += (uint64_t)__builtin_popcountll(bd) / G;
-      gs[4] += (bp | bd) ? 0u : 1u;
-    }
-#endif
     if (phase == PH_RESET) {
       // learn: optional greedy round before episode t (distr_q.py:278-281)
       bool target = false;
@@ -2745,50 +2656,20 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
     const bool dec_ph = phase == PH_POST || phase == PH_DECIDE;
     const bool wave_decides = (int)__builtin_popcountll(__ballot(dec_ph)) >= SFL_TICK_HOLD * G &&
                               (SFL_TICK_REMMIN <= 0 || __ballot(dec_ph && mpopc(v.q_mask) < SFL_TICK_REMMIN) != 0ull);
-#ifdef SFL_PROFILE
-    tp0 = __builtin_amdgcn_s_memtime();
-#endif
     if constexpr (TIMED) tm.lap(TM_OTHER);
     if (phase == PH_TICK && !wave_decides) {
       abytes += 36u * (uint32_t)(m.T - mpopc(v.arr_mask));
       v.tick();
       ticks++;
-      if (v.flags & F_TERM) phase = (v.flags & F_INFLIGHT) ? PH_POST : PH_END;
-      else if (many(v.q_mask)) phase = (v.flags & F_INFLIGHT) ? PH_POST : PH_DECIDE;
+      phase = v.after_tick();
     }
     if constexpr (TIMED) tm.lap(TM_TICK);
-#ifdef SFL_PROFILE
-    {
-      const uint64_t t1 = __builtin_amdgcn_s_memtime();
-      gs[5] += t1 - tp0;
-      tp0 = t1;
-    }
-#endif
     if (phase == PH_POST) {  // post step + loop bookkeeping of the decision in flight
       const bool greedy = (v.flags & F_GREEDY) != 0;
       v.post(d, greedy);
-      if (TRACE && c.trace && (int32_t)e == c.trace_env) {
-        const uint64_t cs = v.sem_checksum();
-        if (v.lane == 0) {
-          const uint64_t n = *c.trace_n;
-          if (n < (uint64_t)c.trace_cap) {
-            uint64_t* tp = c.trace + 4 * n;
-            tp[0] = (uint64_t)(uint32_t)v.now | ((uint64_t)(uint32_t)d.sw << 16) | ((uint64_t)(uint32_t)d.h << 32) |
-                    ((uint64_t)(uint32_t)d.action << 48);
-            tp[1] = (uint64_t)d.state | ((uint64_t)(uint32_t)d.reward << 32);
-            tp[2] = cs;
-            tp[3] = (uint64_t)(uint32_t)d.next_sw;
-          }
-          *c.trace_n = n + 1;
-        }
-      }
-      v.flags &= ~F_INFLIGHT;
-      v.cum += d.reward;
-      v.ep_dec += 1;
-      v.n_dec += 1;
-      v.step_ctr += 1;
-      if (v.step_ctr > max_steps) v.flags |= F_TRUNC;
-      phase = (v.flags & (F_TERM | F_TRUNC)) ? PH_END : PH_DECIDE;
+      if (TRACE && c.trace && (int32_t)e == c.trace_env) v.trace_decision(c, d, v.lane);
+      v.count_decision(d, max_steps);
+      phase = v.after_post();
       if (v.n_dec >= dec_budget) break;
     }
     if constexpr (TIMED) {
@@ -2796,13 +2677,6 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
       v.tm_on = tm.on;
     }
     const uint64_t dec_lanes = TIMED ? (uint64_t)__ballot(phase == PH_DECIDE) : 0ull;
-#ifdef SFL_PROFILE
-    {
-      const uint64_t t1 = __builtin_amdgcn_s_memtime();
-      gs[6] += t1 - tp0;
-      tp0 = t1;
-    }
-#endif
     if (phase == PH_DECIDE) {
       const bool greedy = (v.flags & F_GREEDY) != 0;
       v.template decide<TIMED>(d, greedy);
@@ -2811,9 +2685,6 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
       phase = many(v.q_mask) ? PH_POST : PH_TICK;
     }
     if constexpr (TIMED) tm.decide_done(v, dec_lanes ? __builtin_ctzll(dec_lanes) : -1);
-#ifdef SFL_PROFILE
-    gs[7] += __builtin_amdgcn_s_memtime() - tp0;
-#endif
     if (phase == PH_END) {
       const int arrived = mpopc(v.arr_mask);
       const size_t cap = (size_t)(c.stats_cap > 0 ? c.stats_cap : 1);
@@ -2849,28 +2720,7 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
   }
   v.store(phase);
   if constexpr (TIMED) tm.flush(c);
-#ifdef SFL_PROFILE
-  {  // the counts of the group that left the loop last (it saw every iteration of the wave)
-    uint64_t mx = gs[0];
-    for (int off = 32; off > 0; off >>= 1) mx = max(mx, (uint64_t)__shfl_xor((long long)mx, off, 64));
-    const int src = __builtin_ctzll(__ballot(gs[0] == mx));
-    uint64_t w[8];
-    for (int k = 0; k < 8; ++k) w[k] = (uint64_t)__shfl((long long)gs[k], src, 64);
-    if (__lane_id() == 0)
-      for (int k = 0; k < 8; ++k) atomicAdd(&g_prof[k], (unsigned long long)w[k]);
-    if (v.lane == 0) {  // per group: decide's counters (prefetches, row / pending hits, decisions) and laps
-      for (int k = 3; k < 9; ++k) atomicAdd(&g_prof[5 + k], (unsigned long long)v.prof[k]);
-      for (int k = 0; k < 16; ++k) atomicAdd(&g_prof[16 + k], (unsigned long long)v.lap[k]);
-    }
-  }
-#endif
-  if (v.lane == 0) {
-    st(s.ep_t, e, ep_t);
-    st(s.n_test, e, n_test);
-    if (c.launch_dec) st(c.launch_dec, e, (uint64_t)v.n_dec);
-    if (c.launch_ticks) st(c.launch_ticks, e, (uint64_t)ticks);
-    if (c.launch_bytes) st(c.launch_bytes, e, (uint64_t)abytes);
-  }
+  v.store_launch(c, ep_t, n_test, ticks, abytes, v.lane);
 }
 
 }  // namespace wave

@@ -1,14 +1,16 @@
 """Compare the wave kernels of two built libsfl.so files: VGPRs, SGPRs, spills, scratch, LDS and code size of every
-k_wave / k_wave2 / k_wave_g instantiation, matched by shape (template arguments).  A trailing HPG = false argument
-(the hyperparameter-group switch, csrc/sfl_kwave_g.h) is dropped, so a library with it compares against one from
-before it; HPG = true kernels are listed on their own.  Exit status 1 if a kernel present in both differs.
+k_wave / k_wave2 / k_wave_g / k_wave_part / k_wave2_part instantiation, matched by shape (template arguments).  A
+trailing HPG = false argument (the hyperparameter-group switch, csrc/sfl_kwave_g.h) is dropped, so a library with it
+compares against one from before it; HPG = true kernels are listed on their own.  The "code" column says whether the
+kernel's machine code (the symbol's bytes in its code object's .text) is the same in both, or the same but for
+pc-relative addresses (same_code).  Exit status 1 if a kernel
+present in both differs in a resource field (registers, spills, scratch, LDS); code bytes alone do not fail.
 Usage: python scripts/kres_diff.py OLD.so NEW.so [--md]"""
 import re
+import struct
 import subprocess
 import sys
 import tempfile
-
-import struct
 
 LLVM = "/opt/rocm/lib/llvm/bin/"
 FIELDS = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
@@ -42,48 +44,78 @@ def kernels_of(co):
         f.flush()
         notes = subprocess.run([LLVM + "llvm-readelf", "--notes", f.name], capture_output=True, text=True).stdout
         syms = subprocess.run([LLVM + "llvm-readelf", "-sW", f.name], capture_output=True, text=True).stdout
-    size = {}
+        secs = subprocess.run([LLVM + "llvm-readelf", "-SW", f.name], capture_output=True, text=True).stdout
+    # .text's address and file offset: a kernel's code is the symbol's bytes in it
+    t = re.search(r"\]\s+\.text\s+PROGBITS\s+([0-9a-f]+)\s+([0-9a-f]+)\s+([0-9a-f]+)", secs)
+    t_addr, t_off, t_size = (int(x, 16) for x in t.groups())
+    size, code = {}, {}
     for line in syms.splitlines():
         w = line.split()
         if len(w) >= 8 and w[3] == "FUNC":
-            size[w[7]] = int(w[2], 0)
+            at, n = int(w[1], 16), int(w[2], 0)
+            size[w[7]] = n
+            if t_addr <= at and at + n <= t_addr + t_size:
+                code[w[7]] = (co[t_off + at - t_addr:t_off + at - t_addr + n], at)
     out = {}
     for blk in notes.split("- .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", blk).group(1)
         # (Itanium mangling: k_waveILi8ELi2ELb1E...E -- integer and bool template arguments only)
-        m = re.search(r"\d+(k_wave_g|k_wave2|k_wave)I((?:L[ib]\d+E)+)E", name)
+        m = re.search(r"\d+(k_wave_g|k_wave2_part|k_wave_part|k_wave2|k_wave)I((?:L[ib]\d+E)+)E", name)
         if not m:
             continue
         args = [("true" if v == "1" else "false") if t == "b" else v for t, v in re.findall(r"L([ib])(\d+)E", m.group(2))]
-        full = {"k_wave": 6, "k_wave2": 6, "k_wave_g": 9}[m.group(1)]
+        full = {"k_wave": 6, "k_wave2": 6, "k_wave_g": 9}.get(m.group(1))  # (the part kernels have no HPG argument)
         hpg = len(args) == full and args[-1] == "true"
         if len(args) == full:
             args = args[:-1]
         key = ("HPG " if hpg else "") + m.group(1) + "<" + ",".join(args) + ">"
         vals = [int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in FIELDS]
-        out[key] = vals + [size.get(name, -1)]
+        out[key] = vals + [size.get(name, -1), code.get(name)]
     return out
+
+
+def same_code(x, y):
+    """x, y: a kernel's (bytes, address) in the two libraries.  'identical'; or 'pc-relative only (n)' if they differ
+    in nothing but n literals of an s_add_u32 that follows an s_getpc_b64 -- the offset to an address elsewhere in the
+    code object, which moves with the kernel's place in .text -- and both point at the same address; or 'differs'."""
+    if x is None or y is None or len(x[0]) != len(y[0]):
+        return "differs"
+    if x[0] == y[0]:
+        return "identical"
+    a, b = struct.unpack(f"<{len(x[0]) // 4}I", x[0]), struct.unpack(f"<{len(y[0]) // 4}I", y[0])
+    moved = [i for i in range(len(a)) if a[i] != b[i]]
+    for i in moved:  # words i - 2, i - 1: s_getpc_b64 (SOP1 op 0x1c); SOP2 s_add_u32 (op 0) with src1 = literal (255)
+        if i < 2 or a[i - 2:i] != b[i - 2:i] or (a[i - 2] & 0xFF80FFFF) != 0xBE801C00 or (a[i - 1] & 0xFF80FF00) != 0x8000FF00:
+            return "differs"
+        if (x[1] + 4 * (i - 1) + a[i]) & 0xFFFFFFFF != (y[1] + 4 * (i - 1) + b[i]) & 0xFFFFFFFF:
+            return "differs"
+    return f"pc-relative only ({len(moved)})"
 
 
 def main(old, new, md=False):
     a, b = kernels(old), kernels(new)
-    head = ["kernel", "vgpr", "sgpr", "vspill", "sspill", "scratch", "lds", "code bytes", ""]
-    rows, bad = [], 0
+    head = ["kernel", "vgpr", "sgpr", "vspill", "sspill", "scratch", "lds", "code bytes", "code", ""]
+    rows, bad, recoded = [], 0, 0
+    nf = len(FIELDS)
     for k in sorted(set(a) | set(b)):
         if k in a and k in b:
-            same = a[k] == b[k]
+            same = a[k][:nf] == b[k][:nf]
+            ident = same_code(a[k][-1], b[k][-1])
             bad += not same
-            rows.append([k] + [str(x) if x == y else f"{x} -> {y}" for x, y in zip(a[k], b[k])] + ["equal" if same else "DIFFERS"])
+            recoded += ident == "differs"
+            rows.append([k] + [str(x) if x == y else f"{x} -> {y}" for x, y in zip(a[k][:-1], b[k][:-1])] +
+                        [ident, "equal" if same else "DIFFERS"])
         else:
-            rows.append([k] + [str(x) for x in (a.get(k) or b[k])] + ["old only" if k in a else "new only"])
+            rows.append([k] + [str(x) for x in (a.get(k) or b[k])[:-1]] + ["-", "old only" if k in a else "new only"])
     if md:
         print("| " + " | ".join(head) + " |\n|" + "---|" * len(head))
         for r in rows:
             print("| " + " | ".join(r) + " |")
     else:
         for r in [head] + rows:
-            print(f"{r[0]:64s}" + "".join(f"{x:>12s}" for x in r[1:]))
-    print(f"{sum(1 for k in a if k in b)} kernels in both, {bad} differ")
+            print(f"{r[0]:64s}" + "".join(f"{x:>24s}" for x in r[1:]))
+    print(f"{sum(1 for k in a if k in b)} kernels in both, {len(set(a) ^ set(b))} in one only, {bad} differ in resources, "
+          f"{recoded} in machine code")
     return 1 if bad else 0
 
 

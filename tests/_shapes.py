@@ -127,7 +127,7 @@ PART_STEPS = (40, 75)
 LEARN = dict(n_episodes=2, exploit_freq=2)
 E_MAX = 256 // 8 + 3  # the most envs a case runs (n_envs(8))
 
-# Which kernel instantiation a mode launches (sfl.hip run / part_local).
+# Which kernel instantiation a mode launches (sfl_kwave_g.h sflk::launch / Mode; sfl.hip launch_part_wave).
 INSTANTIATION = dict(plain="plain", trace="trace", timed="timed", trunc="timed", hpg="hpg", part="part")
 
 Case = namedtuple("Case", "row G mode arg", defaults=(None,))  # G None: no SFL_WAVE_G; arg: max_steps / local_rows
