@@ -714,8 +714,11 @@ struct HipBackend {
   }
   int sync() { return check(stream_wait(), "sync") && err.empty() ? 0 : -1; }
   // process-wide, one per device, built on first use and kept for the life of the process
+  // SFL_SEEDSEQ_TABLE=0 (read on every call) runs without it, as a device that cannot hold its 8.6 GB does
   const uint32_t* seedseq_table() {
     static uint32_t* tab[64] = {};
+    const char* sw = getenv("SFL_SEEDSEQ_TABLE");
+    if (sw && atoi(sw) == 0) return nullptr;
     if (dev < 0 || dev >= 64) return nullptr;
     if (!tab[dev]) {
       const uint64_t n = 1ull << 31;

@@ -207,8 +207,15 @@ def predict(c):
     return v, group_lanes(v)
 
 
+# Scenarios that are no ROWS entry (tests/_limits.py derives some from the rows): key -> builder.  Every function below
+# that takes a row takes such a key too.
+DERIVED = {}
+
+
 @functools.lru_cache(maxsize=None)
 def scenario(row):
+    if row in DERIVED:
+        return DERIVED[row]()
     S, T, K, seed = row
     return mapgen.generate(S, T, K, seed=seed, malfunction=(0.01, 5, 15), name="edge")
 
@@ -216,7 +223,7 @@ def scenario(row):
 @functools.lru_cache(maxsize=None)
 def compiled(row):
     cm = comp.compile_scenario(scenario(row))
-    assert (cm.S, cm.T) == row[:2], (row, cm.S, cm.T)
+    assert row in DERIVED or (cm.S, cm.T) == row[:2], (row, cm.S, cm.T)
     return cm
 
 
@@ -243,16 +250,17 @@ def stepped(cm, hp, sds, lib, chunks=CHUNKS, **kw):
 
 
 @functools.lru_cache(maxsize=None)
-def host_plain(row, chunks=CHUNKS, n=E_MAX):
-    b = stepped(compiled(row), HP, seeds(n), hostsim.lib(), chunks)
+def host_plain(row, chunks=CHUNKS, n=E_MAX, max_steps=100_000):
+    b = stepped(compiled(row), HP, seeds(n), hostsim.lib(), chunks, max_steps=max_steps)
     ref = snapshot(b, n)
     b.close()
     return ref
 
 
 @functools.lru_cache(maxsize=None)
-def host_hpg(row, n=E_MAX):
-    b = stepped(compiled(row), HANDLE_HP, hpg_seeds(n), hostsim.lib(), hparam_groups=GROUPS, env_group=env_groups(n))
+def host_hpg(row, n=E_MAX, chunks=CHUNKS, max_steps=100_000):
+    b = stepped(compiled(row), HANDLE_HP, hpg_seeds(n), hostsim.lib(), chunks, hparam_groups=GROUPS,
+                env_group=env_groups(n), max_steps=max_steps)
     ref = snapshot(b, n)
     b.close()
     return ref
@@ -263,10 +271,10 @@ LEARN_KEYS = ("cum_reward", "arrived", "num_malfunctions", "delays", "decisions"
 
 
 @functools.lru_cache(maxsize=None)
-def host_learn(row, max_steps=100_000, n=E_MAX):
+def host_learn(row, max_steps=100_000, n=E_MAX, n_episodes=LEARN["n_episodes"], exploit_freq=LEARN["exploit_freq"]):
     """(learn outputs [episode][...][env], snapshot) of learn(2, exploit_freq=2) on the host build."""
     b = runtime.Batch(compiled(row), HP, seeds(n), lib=hostsim.lib(), ntab=NTAB, max_steps=max_steps)
-    out = b.learn(LEARN["n_episodes"], exploit_freq=LEARN["exploit_freq"])
+    out = b.learn(n_episodes, exploit_freq=exploit_freq)
     ref = snapshot(b, n)
     b.close()
     return out, ref
@@ -274,19 +282,21 @@ def host_learn(row, max_steps=100_000, n=E_MAX):
 
 # ---- references: the oracle, once per (row, seed, hyperparameters) ---------------------------------------------
 @functools.lru_cache(maxsize=None)
-def oracle_plain(row, seed, group=None, total=sum(CHUNKS)):
+def oracle_plain(row, seed, group=None, total=sum(CHUNKS), max_steps=100_000):
     """The oracle's Q dict after ``total`` decisions (``group``: with that entry of GROUPS)."""
-    _, model = so.build(scenario(row), seed, HP if group is None else GROUPS[group], trace=False)
+    _, model = so.build(scenario(row), seed, HP if group is None else GROUPS[group], max_steps=max_steps, trace=False)
     so.run_decisions(model, total)
     return model.q
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_learn(row, seed, max_steps=100_000, trace=False):
-    """learn(2, exploit_freq=2) on the oracle: its outputs, the decisions of each learn episode, the Q dict and (with
-    ``trace``) the per-decision records of tests/_trace.py, exploit episodes included."""
+def oracle_learn(row, seed, max_steps=100_000, trace=False, n_episodes=LEARN["n_episodes"],
+                 exploit_freq=LEARN["exploit_freq"]):
+    """learn(2, exploit_freq=2) on the oracle: its outputs, the decisions of each learn episode, the Q dict, the resets
+    it made (exploit episodes' included) and (with ``trace``) the per-decision records of tests/_trace.py, exploit
+    episodes included."""
     env, model = so.build(scenario(row), seed, HP, max_steps=max_steps, trace=False)
-    recs, decisions, in_test = [], [], [False]
+    recs, decisions, in_test, resets = [], [], [False], [0]
     rec = _trace.oracle_recorder(compiled(row), recs) if trace else None
     inner_test, inner_reset = model.test, env.reset
 
@@ -298,6 +308,7 @@ def oracle_learn(row, seed, max_steps=100_000, trace=False):
             in_test[0] = False
 
     def reset(*a, **kw):
+        resets[0] += 1
         if not in_test[0]:
             decisions.append(0)
         return inner_reset(*a, **kw)
@@ -309,21 +320,23 @@ def oracle_learn(row, seed, max_steps=100_000, trace=False):
             rec(*a)
 
     model.test, env.reset, model.on_step = test, reset, on_step
-    out = model.learn(LEARN["n_episodes"], exploit_freq=LEARN["exploit_freq"])
-    return dict(out=out, decisions=decisions, q=model.q, recs=recs)
+    out = model.learn(n_episodes, exploit_freq=exploit_freq)
+    return dict(out=out, decisions=decisions, q=model.q, recs=recs, resets=resets[0])
 
 
-def learn_mismatches(out, e, ref):
-    """Fields of env e of a batch's learn outputs that differ from the oracle's ``oracle_learn`` result."""
+def learn_mismatches(out, e, ref, n_episodes=LEARN["n_episodes"], exploit_freq=LEARN["exploit_freq"]):
+    """Fields of env e of a batch's learn outputs that differ from the oracle's ``oracle_learn`` result (of the same
+    ``n_episodes`` and ``exploit_freq``)."""
     o = ref["out"]
     # (the batch files an exploit round under the episode it precedes, the reference appends it to a list)
-    xt = [t for t in range(LEARN["n_episodes"]) if (t + 1) % LEARN["exploit_freq"] == 0]
-    assert len(xt) == len(o["cum_reward_exploit"]) == len(o["arrived_trains_exploit"])
+    xt = [t for t in range(n_episodes) if exploit_freq and (t + 1) % exploit_freq == 0]
+    ox = [o.get(k, []) for k in ("cum_reward_exploit", "arrived_trains_exploit")]  # (absent without exploit rounds)
+    assert len(xt) == len(ox[0]) == len(ox[1])
     pairs = [("cum_reward", out["cum_reward"][:, e].tolist(), o["cum_reward"]),
              ("arrived", out["arrived"][:, e].tolist(), o["arrived_trains"]),
              ("num_malfunctions", out["num_malfunctions"][:, e].tolist(), o["num_malfunctions"]),
              ("delays", out["delays"][:, :, e].astype(float).tolist(), [[float(d) for d in ep] for ep in o["delays"]]),
              ("decisions", out["decisions"][:, e].tolist(), ref["decisions"]),
-             ("cum_reward_exploit", out["cum_reward_exploit"][xt, e].tolist(), o["cum_reward_exploit"]),
-             ("arrived_trains_exploit", out["arrived_trains_exploit"][xt, e].tolist(), o["arrived_trains_exploit"])]
+             ("cum_reward_exploit", out["cum_reward_exploit"][xt, e].tolist(), ox[0]),
+             ("arrived_trains_exploit", out["arrived_trains_exploit"][xt, e].tolist(), ox[1])]
     return [(k, a, b) for k, a, b in pairs if a != b]
