@@ -29,6 +29,8 @@
  *                     env.reset / agent_iter / last / step(action) / observe
  *                                                                    switchfl/switch_env.py:93, 616-675
  *                     (driven by any learner, e.g. distr_q.py:302-320)
+ *   sfl_env_begin_wave   sfl_env_begin with the env step on the handle's wave kernel (one env per wavefront
+ *                     or lane group) instead of the lane-per-env body: same calls, same results
  *   sfl_env_step_dev / sfl_env_sync   the same protocol for a policy on the device: device pointers in and
  *                     out, the observation vector of observer.py:269-308 decoded on the device, queued on the
  *                     caller's stream without a wait (the one call that is not synchronous)
@@ -266,6 +268,14 @@ typedef struct {
   int32_t* truncated;      /* episode end: 1 truncation (max_steps), 0 termination */
 } sfl_env_io;
 int sfl_env_begin(sfl_handle* h);
+/* sfl_env_begin with the env step on the wave kernel of the shape the handle was created with (sfl_get_counters:
+ * kernel_variant, group_lanes; a handle created on the LDS-map shape steps the same shape without the LDS tables)
+ * instead of the lane-per-env body.  Every later call -- sfl_env_step, sfl_env_step_dev, sfl_env_sync,
+ * sfl_get_env_state -- is the same and returns the same bits.  Fails, with sfl_get_kernel_note's reason in the
+ * message, on a handle without a wave shape (e.g. more than 256 switches, or SFL_KERNEL=scalar) and on a build
+ * without wave kernels (the host build).  Either begin call may follow the other on one handle: each starts every
+ * env fresh in its own kernel. */
+int sfl_env_begin_wave(sfl_handle* h);
 int sfl_env_step(sfl_handle* h, sfl_env_io* io);
 
 /* ---- external-action mode with the policy on the device: tensors in and out, no host in the loop ----

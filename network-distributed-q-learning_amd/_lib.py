@@ -106,6 +106,7 @@ EXPORTS = {
     "sfl_get_kernel_note": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     # external-action mode (aec.py) and the per-phase device time (distr_q.py timing accumulators)
     "sfl_env_begin": (C.c_int, [C.c_void_p]),
+    "sfl_env_begin_wave": (C.c_int, [C.c_void_p]),
     "sfl_env_step": (C.c_int, [C.c_void_p, P(EnvIO)]),
     "sfl_env_step_dev": (C.c_int, [C.c_void_p, P(EnvDevIO)]),
     "sfl_env_sync": (C.c_int, [C.c_void_p]),

@@ -9,11 +9,14 @@ observation the previous call emitted and runs the env on to its next decision (
 device, for all E envs at once.  ``ASyncSwitchEnv`` (env.py) wraps env 0 of an ``AECBatch`` in the
 reference's single-env methods.  For a policy that lives on the same GPU, ``AECBatch.step_torch`` / ``sync``
 (``sfl_env_step_dev`` / ``sfl_env_sync``) are the same step with torch tensors on the device in and out, the
-observation vector decoded on the device, and no host wait.
+observation vector decoded on the device, and no host wait.  ``kernel="wave"`` (or
+``SFL_ENV_KERNEL=wave``) runs the same env step on the handle's wave kernel -- one env per wavefront or lane group,
+``sfl_env_begin_wave`` -- instead of the lane-per-env body: same calls, same results.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -37,13 +40,27 @@ class AECBatch:
     mask bits), ``reward`` (last()'s reward of (switch, train)), ``now``; for the action applied in this
     call ``next_switch`` and ``step_now`` (-1 if none); ``arrived`` (bitmask, 4 words); at an episode end
     ``malfunctions``, ``delays`` [T] and ``truncated``.
+
+    ``kernel``: ``"lane"`` -- the lane-per-env body (``sfl_env_begin``) --, ``"wave"`` -- the wave kernel of the
+    handle's shape (``sfl_env_begin_wave``; ``batch.counters()`` reports ``kernel_variant`` and ``group_lanes``) --
+    or None: ``os.environ.get("SFL_ENV_KERNEL", "lane")``, read at creation like ``SFL_KERNEL`` and ``SFL_WAVE_G``.
+    Both give the same outputs bit for bit.  ``"wave"`` raises ``SflError`` with the library's reason where it cannot
+    be honoured (a map without a wave shape, ``SFL_KERNEL=scalar``, the host build); any other value ``ValueError``.
     """
+
+    KERNELS = ("lane", "wave")
 
     FIELDS = ("agent", "train", "slot", "state", "mask", "reward", "now", "next_switch", "step_now", "malfunctions",
               "truncated")
 
     def __init__(self, cm: CompiledMap, seeds: Sequence[int], lib: Optional[_lib.Lib] = None, device: int = 0,
-                 max_steps: int = 100_000, malfunction_stream: str = "counter", delay_threshold: int = 20):
+                 max_steps: int = 100_000, malfunction_stream: str = "counter", delay_threshold: int = 20,
+                 kernel: Optional[str] = None):
+        if kernel is None:
+            kernel = os.environ.get("SFL_ENV_KERNEL", "lane")
+        if kernel not in self.KERNELS:
+            raise ValueError(f"AECBatch: kernel {kernel!r} is none of {self.KERNELS}")
+        self.kernel = kernel
         self.cm = cm
         self.batch = Batch(cm, _ENV_HP, seeds, lib=lib, device=device, max_steps=max_steps, ntab=16,
                            malfunction_stream=malfunction_stream, delay_threshold=delay_threshold)
@@ -64,7 +81,14 @@ class AECBatch:
         self._t = None            # step_torch's tensors and descriptor (made by its first call)
         self._stream = None       # the stream last handed to the library (step_torch on a HIP device)
         self._host_stale = False  # device steps ran since the host arrays (self.out) were last filled
-        self.lib.check(self.lib.dll.sfl_env_begin(self.batch.h), "sfl_env_begin")
+        try:
+            if kernel == "wave":
+                self.lib.check(self.lib.dll.sfl_env_begin_wave(self.batch.h), "sfl_env_begin_wave")
+            else:
+                self.lib.check(self.lib.dll.sfl_env_begin(self.batch.h), "sfl_env_begin")
+        except Exception:
+            self.batch.close()
+            raise
 
     def close(self):
         self.batch.close()

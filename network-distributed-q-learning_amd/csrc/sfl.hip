@@ -665,17 +665,23 @@ struct HipBackend {
     *ms = t;
     return err.empty() ? 0 : -1;
   }
+  // external-action mode's env step: the handle's wave kernel (sfl_env_begin_wave: variant > 0), else k_run_ext
+  void launch_ext(int variant, const sfl::SflMap& m, uint32_t E, const sfl::SflMap* pm, const sfl::SflState* ps,
+                  const sfl::SflCtl* pc) {
+    const unsigned blocks = (E + 63) / 64;  // (64-thread blocks: few envs, spread over the CUs)
+    if (variant >= 1 && variant < sfl::kNumVariants) sflk::launch({variant, sflk::Mode::Ext, E, stream, pm, ps, pc});
+    else if (m.T <= 32) k_run_ext<1><<<blocks, 64, 0, stream>>>(pm, ps, pc);
+    else if (m.T <= 64) k_run_ext<2><<<blocks, 64, 0, stream>>>(pm, ps, pc);
+    else k_run_ext<4><<<blocks, 64, 0, stream>>>(pm, ps, pc);
+  }
   // external-action mode: one call = every env applies its action and runs to its next observation
-  int run_ext(const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c, float* ms) {
+  int run_ext(const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c, int variant, float* ms) {
     const ParamBlock3* dp = upload_params(m, s, c);
     const sfl::SflMap* pm = &dp->m;
     const sfl::SflState* ps = &dp->s;
     const sfl::SflCtl* pc = &dp->c;
     check(hipEventRecord(ev0, stream), "event");
-    const unsigned blocks = (s.E + 63) / 64;  // (64-thread blocks: few envs, spread over the CUs)
-    if (m.T <= 32) k_run_ext<1><<<blocks, 64, 0, stream>>>(pm, ps, pc);
-    else if (m.T <= 64) k_run_ext<2><<<blocks, 64, 0, stream>>>(pm, ps, pc);
-    else k_run_ext<4><<<blocks, 64, 0, stream>>>(pm, ps, pc);
+    launch_ext(variant, m, s.E, pm, ps, pc);
     if (!check(hipGetLastError(), "k_run_ext launch")) return -1;
     check(hipEventRecord(ev1, stream), "event");
     if (!check(event_wait(ev1), "k_run_ext")) return -1;
@@ -693,7 +699,7 @@ struct HipBackend {
   ExtParams ep_host;
   bool ep_valid = false;
   int run_ext_dev(const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c, const sfl::SflExt& x,
-                  const sfl::SflEnc& enc) {
+                  const sfl::SflEnc& enc, int variant) {
     static_assert(sizeof(ExtParams) <= 4096, "params");
     if (!d_eparams && !check(hipMalloc(&d_eparams, 4096), "hipMalloc params")) return -1;
     auto* dp = (ExtParams*)d_eparams;
@@ -702,10 +708,7 @@ struct HipBackend {
     hp.c.ext = &dp->t;
     hp.t = x;
     if (!sync_params(dp, ep_host, ep_valid, hp)) return -1;
-    const unsigned blocks = (s.E + 63) / 64;  // (as run_ext)
-    if (m.T <= 32) k_run_ext<1><<<blocks, 64, 0, stream>>>(&dp->m, &dp->s, &dp->c);
-    else if (m.T <= 64) k_run_ext<2><<<blocks, 64, 0, stream>>>(&dp->m, &dp->s, &dp->c);
-    else k_run_ext<4><<<blocks, 64, 0, stream>>>(&dp->m, &dp->s, &dp->c);
+    launch_ext(variant, m, s.E, &dp->m, &dp->s, &dp->c);
     if (!check(hipGetLastError(), "k_run_ext launch")) return -1;
     const unsigned eblocks = (unsigned)(((size_t)enc.E * sfl::OBS_PAIRS + 255) / 256);
     k_env_encode<<<eblocks, 256, 0, stream>>>(enc);

@@ -142,6 +142,11 @@ int sfl_env_begin(sfl_handle* h) {
   return sfl::env_begin(HH(h));
 }
 
+int sfl_env_begin_wave(sfl_handle* h) {
+  if (!h) return sfl::fail("sfl_env_begin_wave: null handle");
+  return sfl::env_begin(HH(h), true);
+}
+
 int sfl_env_step(sfl_handle* h, sfl_env_io* io) {
   if (!h) return sfl::fail("sfl_env_step: null handle");
   return sfl::env_step(HH(h), io);

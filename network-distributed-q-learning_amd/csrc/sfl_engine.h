@@ -55,6 +55,8 @@ struct Handle {
   float last_kernel_ms = 0.f;
   std::vector<std::vector<uint32_t>> keep;  // host sources of async uploads, alive until the create() sync
   int variant = 0;  // 0: k_run (lane per env); v > 0: k_wave shape kVariants[v] (see choose_variant)
+  int created_variant = 0;  // choose_variant's row at create: sfl_env_begin puts the handle on the lane-per-env body
+                            // (variant = 0), sfl_env_begin_wave back on this row (ext_variant)
   std::string variant_note;  // why a device handle runs k_run ("" when k_wave, or when chosen explicitly)
   // host copies of the map fields the partitioned mode lays out its owned Q blocks with
   std::vector<uint8_t> h_sw_np, h_q_w;
@@ -232,7 +234,7 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
   h->h_q_w.assign(md->q_w, md->q_w + (size_t)md->S * 4);
   h->h_q_off.assign(md->q_off, md->q_off + (size_t)md->S * 4);
   h->h_row_base.assign(md->row_base, md->row_base + (size_t)md->S * 4);
-  h->variant = choose_variant(md, B::kHasWave, &h->variant_note, n_envs);
+  h->variant = h->created_variant = choose_variant(md, B::kHasWave, &h->variant_note, n_envs);
   SflMap& m = h->map;
   const size_t HW = (size_t)md->H * md->W, NP = (size_t)md->S * 4, S = md->S, T = md->T;
   m.H = md->H;
@@ -797,10 +799,32 @@ int run(Handle<B>* h, const SflCtl& c_in, sfl_run_args* args) {
 // ---------------------------------------------------------------------------
 // external-action mode (include/sfl.h sfl_env_begin / sfl_env_step; SflExt in sfl_core.h)
 // ---------------------------------------------------------------------------
+// the row of external-action mode's wave kernel for a handle created on row v: v itself, but for the LM row its twin
+// without the LDS map tables (copying 64 KB of tables per block buys nothing for one decision per launch)
+inline int ext_variant(int v) {
+  if (v <= 0 || !kVariants[v].LM) return v;
+  for (int u = 1; u < kNumVariants; ++u) {
+    const WaveShape &a = kVariants[u], &b = kVariants[v];
+    if (!a.LM && a.PPL == b.PPL && a.SPL == b.SPL && a.TW == b.TW && a.G == b.G) return u;
+  }
+  return 0;
+}
+
+// wave: sfl_env_begin_wave -- the same fresh start on the wave shape the handle was created with (EXT in sfl_wave.h)
 template <class B>
-int env_begin(Handle<B>* h) {
-  if (h->part.world) return fail("sfl_env_begin: the handle is graph-partitioned");
-  if (h->map.env_group) return fail("sfl_env_begin: the handle has hyperparameter groups (sfl_set_hparam_groups)");
+int env_begin(Handle<B>* h, bool wave = false) {
+  const std::string fn = wave ? "sfl_env_begin_wave" : "sfl_env_begin";
+  if (h->part.world) return fail(fn + ": the handle is graph-partitioned");
+  if (h->map.env_group) return fail(fn + ": the handle has hyperparameter groups (sfl_set_hparam_groups)");
+  int variant = 0;
+  if (wave) {
+    if (!B::kHasWave)
+      return fail(fn + ": this build has no wave kernels (the host build runs the lane-per-env body only)");
+    variant = ext_variant(h->created_variant);
+    if (variant <= 0)
+      return fail(fn + ": the handle has no wave shape (" +
+                  (h->variant_note.empty() ? std::string("SFL_KERNEL=scalar") : h->variant_note) + ")");
+  }
   const size_t E = h->E, T = h->map.T, S = h->map.S, NP = h->map.NP;
   if (!h->d_ext) {
     SflExt& x = h->ext;
@@ -821,11 +845,12 @@ int env_begin(Handle<B>* h) {
     h->d_ext = h->template dalloc<SflExt>(1);
     if (!x.actions || !x.agent || !x.train || !x.slot || !x.state || !x.mask || !x.reward || !x.now || !x.next_sw ||
         !x.step_now || !x.arrived || !x.n_mf || !x.delays || !x.truncated || !h->d_ext)
-      return fail("sfl_env_begin: allocation failed");
+      return fail(fn + ": allocation failed");
     h->be.h2d(h->d_ext, &h->ext, sizeof(SflExt));
   }
-  // a fresh env (a new ASyncSwitchEnv): the lane-per-env body and its state layout, every env at reset
-  h->variant = 0;
+  // a fresh env (a new ASyncSwitchEnv): the lane-per-env body and its state layout, or the wave shape and its
+  // env-major one (the memsets below do not depend on the layout), every env at reset
+  h->variant = variant;
   h->env_mode = true;
   SflState& st = h->st;
   std::vector<int32_t> ph(E, PH_RESET);
@@ -868,7 +893,7 @@ int env_step(Handle<B>* h, sfl_env_io* io) {
   c.launch_ticks = h->d_launch_ticks;
   c.launch_bytes = h->d_launch_bytes;
   float ms = 0.f;
-  if (h->be.run_ext(h->map, h->st, c, &ms)) return fail(std::string("sfl_env_step: ") + h->be.error());
+  if (h->be.run_ext(h->map, h->st, c, h->variant, &ms)) return fail(std::string("sfl_env_step: ") + h->be.error());
   h->last_kernel_ms = ms;
   auto get = [&](void* dst, const void* src, size_t n) {
     if (dst) h->be.d2h_async(dst, src, n);
@@ -944,7 +969,7 @@ int env_step_dev(Handle<B>* h, const sfl_env_dev_io* dio) {
   c.launch_dec = h->d_launch_dec;
   c.launch_ticks = h->d_launch_ticks;
   c.launch_bytes = h->d_launch_bytes;
-  if (h->be.run_ext_dev(h->map, h->st, c, x, enc)) return fail(std::string("sfl_env_step_dev: ") + h->be.error());
+  if (h->be.run_ext_dev(h->map, h->st, c, x, enc, h->variant)) return fail(std::string("sfl_env_step_dev: ") + h->be.error());
   return 0;
 }
 

@@ -58,7 +58,7 @@ struct HostBackend {
     *ms = 0.f;
     return 0;
   }
-  int run_ext(const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c, float* ms) {
+  int run_ext(const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c, int /*variant*/, float* ms) {
 #pragma omp parallel for schedule(dynamic, 1)
     for (int64_t e = 0; e < (int64_t)s.E; ++e) {
       if (m.T <= 32) sfl::env_run_ext<1>(m, s, c, (uint32_t)e);
@@ -71,10 +71,10 @@ struct HostBackend {
   // sfl_env_step_dev: the env step into the caller's buffers ("device" memory is host memory here), then
   // k_env_encode's items as a loop
   int run_ext_dev(const sfl::SflMap& m, const sfl::SflState& s, sfl::SflCtl c, const sfl::SflExt& x,
-                  const sfl::SflEnc& enc) {
+                  const sfl::SflEnc& enc, int variant) {
     c.ext = &x;
     float ms = 0.f;
-    run_ext(m, s, c, &ms);
+    run_ext(m, s, c, variant, &ms);
     const int64_t n = (int64_t)enc.E * sfl::OBS_PAIRS;
 #pragma omp parallel for
     for (int64_t t = 0; t < n; ++t) sfl::env_encode_item(enc, (uint32_t)t);

@@ -4,8 +4,8 @@
 // block.  k_wave / k_wave2: one env per wavefront (sfl_wave.h run).  Which unit compiles which kernel: owner()
 // below -- variant 7 (the bench's c3 shape) in sfl_kwave_v7.hip with the register-minimising scheduler, the
 // HPG = true kernels (hyperparameter groups, sfl_set_hparam_groups: the plain launch of every shape) in
-// sfl_kwave_hpg.hip and -- variant 7 -- sfl_kwave_hpg_v7.hip, so that they compile in parallel with sfl.hip, which
-// has all the others.
+// sfl_kwave_hpg.hip and -- variant 7 -- sfl_kwave_hpg_v7.hip, the EXT = true kernels (external-action mode,
+// sfl_env_begin_wave) in sfl_kwave_ext.hip, so that they compile in parallel with sfl.hip, which has all the others.
 //
 // Waves per SIMD the grouped kernel is register-budgeted for (sfl::kVariants[v].OCC): shapes with one train
 // slot per lane (TW <= G) 4 -- c2 (variant 6): 918 M vs 805 M at 3 (VGPR-bound, spills a little; 5: 589 M) --,
@@ -33,35 +33,40 @@ namespace sflk {
 // registers per lane (sfl::kVariants).
 // TIMED: the learn() / test() instantiation, with the sampled phase timers (sfl_wave.h PhaseTimer); the
 // benchmark's sfl_step runs the untimed one
-template <int PPL, int SPL, int TW, bool TRACE, bool TIMED = false, bool HPG = false>
+// EXT: external-action mode's env step (sfl_env_begin_wave; WEnv::ext_run), one decision per launch
+template <int PPL, int SPL, int TW, bool TRACE, bool TIMED = false, bool HPG = false, bool EXT = false>
 __global__ void __launch_bounds__(SFL_WAVE_BLOCK) __attribute__((amdgpu_waves_per_eu(SFL_WAVE_OCC))) k_wave(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict__ s,
                                               const sfl::SflCtl* __restrict__ c) {
-  sfl::wave::run<PPL, SPL, TW, TRACE, false, TIMED, HPG>(*m, *s, *c);
+  sfl::wave::run<PPL, SPL, TW, TRACE, false, TIMED, HPG, EXT>(*m, *s, *c);
 }
-template <int PPL, int SPL, int TW, bool TRACE, bool TIMED = false, bool HPG = false>
+template <int PPL, int SPL, int TW, bool TRACE, bool TIMED = false, bool HPG = false, bool EXT = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SFL_WAVE2_OCC))) k_wave2(const sfl::SflMap* __restrict__ m,
                                                                                    const sfl::SflState* __restrict__ s,
                                                                                    const sfl::SflCtl* __restrict__ c) {
-  sfl::wave::run<PPL, SPL, TW, TRACE, false, TIMED, HPG>(*m, *s, *c);
+  sfl::wave::run<PPL, SPL, TW, TRACE, false, TIMED, HPG, EXT>(*m, *s, *c);
 }
 
-template <int PPL, int SPL, int TW, bool TRACE, int G, int OCC, bool TIMED = false, bool LM = false, bool HPG = false>
+template <int PPL, int SPL, int TW, bool TRACE, int G, int OCC, bool TIMED = false, bool LM = false, bool HPG = false, bool EXT = false>
 __global__ void __launch_bounds__(SFL_GROUP_BLOCK) __attribute__((amdgpu_waves_per_eu(OCC)))
 k_wave_g(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict__ s, const sfl::SflCtl* __restrict__ c) {
-  sfl::wave::run_groups<PPL, SPL, TW, TRACE, G, TIMED, LM, HPG>(*m, *s, *c);
+  sfl::wave::run_groups<PPL, SPL, TW, TRACE, G, TIMED, LM, HPG, EXT>(*m, *s, *c);
 }
 
 // ---- one launch path from the shape table ---------------------------------------------------------------------
 // A cell = a row v of sfl::kVariants (1 .. kNumVariants - 1) x a launch mode.  Everything about a cell follows from
 // the row: its kernel family, its grid and block, and the translation unit that compiles it.
 static_assert(sizeof(sfl::kVariants) / sizeof(sfl::kVariants[0]) == sfl::kNumVariants, "kNumVariants counts kVariants' rows");
-enum class Mode { Plain, Trace, Timed, Hpg };  // Hpg: a handle with hyperparameter groups (plain only)
-// libsfl.so's translation units (build.TUS): sfl.hip, sfl_kwave_v7.hip, sfl_kwave_hpg.hip, sfl_kwave_hpg_v7.hip
-enum class Unit { Main, V7, Hpg, HpgV7 };
+// Hpg: a handle with hyperparameter groups (plain only); Ext: a handle in external-action mode on the wave kernels
+// (sfl_env_begin_wave) -- every row but the LM one, whose handles step the same shape without the LDS tables
+enum class Mode { Plain, Trace, Timed, Hpg, Ext };
+// libsfl.so's translation units (build.TUS): sfl.hip, sfl_kwave_v7.hip, sfl_kwave_hpg.hip, sfl_kwave_hpg_v7.hip,
+// sfl_kwave_ext.hip
+enum class Unit { Main, V7, Hpg, HpgV7, Ext };
 constexpr int kSchedVariant = 7;  // the bench's c3 shape: its units are built with the register-minimising scheduler
 // the unit that owns a cell: it alone instantiates the cell's kernel, with its own compiler flags.  Every cell has
 // exactly one owner (this function's value); a unit that does not define its launch_unit fails the link.
 constexpr Unit owner(int v, Mode md) {
+  if (md == Mode::Ext) return Unit::Ext;
   if (md == Mode::Hpg) return v == kSchedVariant ? Unit::HpgV7 : Unit::Hpg;
   return v == kSchedVariant ? Unit::V7 : Unit::Main;
 }
@@ -86,20 +91,22 @@ template <Unit U, int V, Mode MD>
 inline void launch_cell(const Launch& l) {
   if constexpr (owner(V, MD) == U) {
     constexpr sfl::WaveShape w = sfl::kVariants[V];
-    constexpr bool TRACE = MD == Mode::Trace, TIMED = MD == Mode::Timed, HPG = MD == Mode::Hpg;
+    constexpr bool TRACE = MD == Mode::Trace, TIMED = MD == Mode::Timed, HPG = MD == Mode::Hpg, EXT = MD == Mode::Ext;
     if (l.variant != V || l.mode != MD) return;
-    if constexpr (w.G < 64)
-      k_wave_g<w.PPL, w.SPL, w.TW, TRACE, w.G, w.OCC, TIMED, (bool)w.LM, HPG><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
+    if constexpr (EXT && w.LM)
+      return;  // (no such cell: ext_variant maps the row to its twin)
+    else if constexpr (w.G < 64)
+      k_wave_g<w.PPL, w.SPL, w.TW, TRACE, w.G, w.OCC, TIMED, (bool)w.LM, HPG, EXT><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
     else if constexpr (two_slot(w))
-      k_wave2<w.PPL, w.SPL, w.TW, TRACE, TIMED, HPG><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
+      k_wave2<w.PPL, w.SPL, w.TW, TRACE, TIMED, HPG, EXT><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
     else
-      k_wave<w.PPL, w.SPL, w.TW, TRACE, TIMED, HPG><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
+      k_wave<w.PPL, w.SPL, w.TW, TRACE, TIMED, HPG, EXT><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
   }
 }
 template <Unit U, int... I>
 inline void launch_owned(const Launch& l, std::integer_sequence<int, I...>) {
   ((launch_cell<U, I + 1, Mode::Plain>(l), launch_cell<U, I + 1, Mode::Trace>(l), launch_cell<U, I + 1, Mode::Timed>(l),
-    launch_cell<U, I + 1, Mode::Hpg>(l)), ...);
+    launch_cell<U, I + 1, Mode::Hpg>(l), launch_cell<U, I + 1, Mode::Ext>(l)), ...);
 }
 // a unit's launches: declared here, defined (SFL_KWAVE_UNIT) in the unit itself
 template <Unit U>
@@ -112,6 +119,8 @@ template <>
 void launch_unit<Unit::Hpg>(const Launch& l);
 template <>
 void launch_unit<Unit::HpgV7>(const Launch& l);
+template <>
+void launch_unit<Unit::Ext>(const Launch& l);
 #define SFL_KWAVE_UNIT(U)                                                                           \
   template <>                                                                                       \
   void sflk::launch_unit<sflk::Unit::U>(const sflk::Launch& l) {                                    \
@@ -124,6 +133,7 @@ inline void launch(const Launch& l) {
     case Unit::V7: return launch_unit<Unit::V7>(l);
     case Unit::Hpg: return launch_unit<Unit::Hpg>(l);
     case Unit::HpgV7: return launch_unit<Unit::HpgV7>(l);
+    case Unit::Ext: return launch_unit<Unit::Ext>(l);
   }
 }
 

@@ -308,9 +308,15 @@ struct PortRec {
 // LM (run_groups only, sfl_engine.h variant 11): the map's move table and distance map (int16) live in the block's LDS
 // HPG: hyperparameter groups (sfl_set_hparam_groups): the env's epsilon and lr schedule are its group's -- row
 // env_group[e] of the [n_groups][ntab] tables and of the [n_groups][4] scalars -- instead of the map's own
-template <int PPL, int SPL, int TWc, bool PART = false, int G = 64, bool LM = false, bool HPG = false>
+// EXT: external-action mode (sfl_env_begin_wave; env_run_ext in sfl_core.h): the env alone, one decision per launch,
+// the action from the caller (SflExt).  PART's control shape with the caller as the row's owner: a decision is
+// observed and emitted in one launch (decide() returns true, F_EXT_OBS) and applied in the next after observing it
+// again.  No learner: no Q-table, key set, epsilon / lr table, epsilon-greedy stream or interaction counters are
+// read or written; the staging holds the deciding train's record only, and only its slot word and distances
+template <int PPL, int SPL, int TWc, bool PART = false, int G = 64, bool LM = false, bool HPG = false, bool EXT = false>
 struct WEnv {
   static_assert(!(HPG && PART), "hyperparameter groups are not part of the partitioned local step");
+  static_assert(!(EXT && (PART || HPG || LM)), "external-action mode: the plain shapes only");
   static_assert(G == 64 || G == 32 || G == 16 || G == 8, "lane group of 8, 16, 32 or 64 lanes");
   static_assert(G == 64 || !PART, "the partitioned local step runs one env per wavefront");
   const SflMap& m;
@@ -328,14 +334,14 @@ struct WEnv {
   // SIMD in 128 VGPRs (1 spilled): 598 M -> 729 M agent-env-steps/s (ring of 32: 673 M).  c3 (G = 16):
   // off by default, see SFL_PF_RING
   static constexpr int RING_N = G < 64 ? SFL_PF_RING : SFL_PF_RING64;
-  static constexpr bool RING = !PART && TPL > 1 && RING_N > 0 && RING_N < TWc;
-  static constexpr int PF_SLOTS = PART ? 1 : (RING ? RING_N : TWc);
+  static constexpr bool RING = !PART && !EXT && TPL > 1 && RING_N > 0 && RING_N < TWc;
+  static constexpr int PF_SLOTS = (PART || EXT) ? 1 : (RING ? RING_N : TWc);
   // (SFL_EPS_PF) the record's doubles: + the staged epsilon
   // (HPG: the staging reads the map's own table, so grouped handles decide on the loaded value)
-  static constexpr bool EPS_PF = SFL_EPS_PF && !PART && G < 64 && G * SPL <= 64 && !HPG;
+  static constexpr bool EPS_PF = SFL_EPS_PF && !PART && !EXT && G < 64 && G * SPL <= 64 && !HPG;
   static constexpr int PFD = EPS_PF ? PF_D + 1 : PF_D;
   static constexpr int PFW = 2 * PFD + PF_WI;
-  __device__ __forceinline__ static int pfx(int h) { return PART ? 0 : h; }
+  __device__ __forceinline__ static int pfx(int h) { return (PART || EXT) ? 0 : h; }
   // RING: record i is staged by lane i % G (register slot i / G) in one pass per G records -- the lanes
   // stage the batch's queued trains in queue order, so a batch of up to G decisions is one set of
   // dependent loads instead of one per train slot; otherwise train h's lane stages it (slot h / G)
@@ -443,6 +449,9 @@ struct WEnv {
       const size_t ge = (size_t)P_->env_base + e_;
       qb = P_->q_own + ge * P_->q_own_per_env;
       touchb = P_->touched_own + ge * P_->own_words;
+    } else if constexpr (EXT) {  // (no learner)
+      qb = nullptr;
+      touchb = nullptr;
     } else {
       qb = s.q + (size_t)e * m.q_per_env;
       touchb = s.touched + (size_t)e * m.touched_words;
@@ -886,7 +895,7 @@ struct WEnv {
 #pragma unroll
     for (int k = 0; k < PPL; ++k) rw[k] = ld(sem_words(), pix(k * G + lane < m.NP ? k * G + lane : 0));
 #pragma unroll
-    for (int k = 0; k < SPL; ++k) nw[k] = ld(s.counts, cix(k * G + lane < m.S ? k * G + lane : 0));
+    for (int k = 0; k < SPL; ++k) nw[k] = EXT ? 0u : ld(s.counts, cix(k * G + lane < m.S ? k * G + lane : 0));
 #pragma unroll
     for (int k = 0; k < TPL; ++k) {
       const int hk = lane + G * k;
@@ -926,7 +935,7 @@ struct WEnv {
       if constexpr (PART) lsem0[k * G + lane] = r;
     }
 #pragma unroll
-    for (int k = 0; k < SPL; ++k) {
+    for (int k = 0; !EXT && k < SPL; ++k) {
       const uint32_t n = k * G + lane < m.S ? nw[k] : 0u;
       lcnt[k * G + lane] = n;
     }
@@ -984,7 +993,7 @@ struct WEnv {
     arr_mask = mask(1);
     fl_mask = mask(2);
     mf_mask = mask(3);
-    if (lane < 5) lrng[lane] = ld(s.rng, ix((size_t)lane));
+    if (!EXT && lane < 5) lrng[lane] = ld(s.rng, ix((size_t)lane));
     cum = (int64_t)Ud(ld(s.cum_reward, e));
     n_mf = U(ld(s.n_mf, e));
     ep_dec = U(ld(s.ep_dec, e));
@@ -1037,7 +1046,7 @@ struct WEnv {
       if constexpr (PART) r0[k] = lsem0[k * G + lane];
     }
 #pragma unroll
-    for (int k = 0; k < SPL; ++k) {
+    for (int k = 0; !EXT && k < SPL; ++k) {
       nw[k] = lcnt[k * G + lane];
       if constexpr (PART) n0[k] = (ldirty[(k * G + lane) >> 5] >> ((k * G + lane) & 31)) & 1u;
     }
@@ -1049,7 +1058,7 @@ struct WEnv {
 #pragma unroll
     for (int k = 0; k < SPL; ++k) {
       const int sw = k * G + lane;
-      if (sw < m.S && (!PART || n0[PART ? k : 0] != 0u)) st(s.counts, cix(sw), nw[k]);
+      if (!EXT && sw < m.S && (!PART || n0[PART ? k : 0] != 0u)) st(s.counts, cix(sw), nw[k]);
     }
     uint32_t err = 0;
 #pragma unroll
@@ -1079,9 +1088,11 @@ struct WEnv {
       put(1, arr_mask);
       put(2, fl_mask);
       put(3, mf_mask);
-      st(s.rng, ix(0), lrng[0]);
-      st(s.rng, ix(1), lrng[1]);
-      st(s.rng, ix(4), lrng[4]);
+      if constexpr (!EXT) {
+        st(s.rng, ix(0), lrng[0]);
+        st(s.rng, ix(1), lrng[1]);
+        st(s.rng, ix(4), lrng[4]);
+      }
       st(s.cum_reward, e, (double)cum);
       st(s.n_mf, e, n_mf);
       st(s.ep_dec, e, ep_dec);
@@ -1553,11 +1564,12 @@ struct WEnv {
     // hold twice the registers; the slot's registers are selected by value, not indexed
     // PART: a launch decides one train per env (the round ends at the next request, and the staging
     // does not survive the launch): stage that train only
-    const int h_first = PART ? mctz(q_mask) : -1;
+    // EXT: likewise the train whose action the launch applies
+    const int h_first = (PART || EXT) ? mctz(q_mask) : -1;
 #pragma unroll 1
     for (int k = 0; k < TPL; ++k) {
       if (!mbit(q_mask, lid() + G * k)) continue;
-      if (PART && lid() + G * k != h_first) continue;
+      if ((PART || EXT) && lid() + G * k != h_first) continue;
       uint32_t roff, qoff;
       prefetch_slot(lid() + G * k, pfx(lid() + G * k), pick(sdec, k), pick(nprv, k), pick(bits, k), pick(pos, k),
                     pick(plan, k), malf, greedy, roff, qoff);
@@ -1676,10 +1688,10 @@ struct WEnv {
     const bool row_ok = pos_k >= 0 && dd < DIST_INF && (pin >> 2) == sw && slot < np;
     const uint32_t qoff = pp[3] + ((pend >> 14) & 0x3FFFu) * (pp[1] >> 16) + ((pend >> 28) & 3u);
     // level 3: Q values
-    // (PART: the rows live on their owners; nothing is staged)
+    // (PART: the rows live on their owners; nothing is staged.  EXT: there are none)
     double rv[4] = {0.0, 0.0, 0.0, 0.0};
     double qv = 0.0;
-    if constexpr (!PART) {
+    if constexpr (!PART && !EXT) {
       const double* rp = qbase() + (row_ok ? roff : 0u);
 #pragma unroll
       for (int c = 0; c < 4; ++c) rv[c] = ld(rp, (size_t)((uint32_t)c < w ? c : 0));
@@ -1730,8 +1742,8 @@ struct WEnv {
     pfl[1] = __longlong_as_double((long long)slw);
     pfi[0] = d16(dd) | (d16(d_stop) << 16);
     pfi[1] = d16(d_rt[1]) | (d16(d_rt[2]) << 16);
-    roff_out = (row_ok && !PART) ? roff : PF_NONE;
-    qoff_out = (hp && !PART) ? qoff : PF_NONE;
+    roff_out = (row_ok && !PART && !EXT) ? roff : PF_NONE;
+    qoff_out = (hp && !PART && !EXT) ? qoff : PF_NONE;
   }
   // a Q cell of this env was written (uniform offset): drop staged copies that contain it
   __device__ __forceinline__ void pf_written(uint32_t off) {
@@ -1744,7 +1756,11 @@ struct WEnv {
 
   // ---- decision (wave-uniform): observe (observer.py:246-308), epsilon-greedy
   //      (distr_q.py:312-319), _apply_action (switch_env.py:203-294) ---------------------------
-  struct Dec {  // (a driver starts from the zero record: no decision in flight)
+  struct DecExt {
+    uint32_t amask = 0;  // EXT: the action mask of an emitted observation
+  };
+  struct DecNone {};
+  struct Dec : std::conditional<EXT, DecExt, DecNone>::type {  // (a driver starts from the zero record: no decision in flight)
     int sw = 0, h = 0, slot = 0;
     uint32_t state = 0;
     int action = 0, j = 0;
@@ -1763,12 +1779,25 @@ struct WEnv {
   // PART: true = observe pass (no reply yet): the request went to the row's owner and nothing of
   // the env changed (the next launch repeats the observation, which is deterministic, and
   // applies the reply)
+  // EXT: x_act = the caller's action for this env, x_open = the env's observation is out and no action has been
+  // applied in this launch.  true = the observation was emitted into d (sw, h, slot, state, amask, reward) and
+  // nothing of the env changed but F_EXT_OBS; false = x_act was applied to it (env_run_ext's two branches).  An
+  // action outside the switch's action space is refused before it touches the env: E_BAD_ACTION, and the
+  // observation is emitted again
   template <bool TM = false>
-  __device__ __forceinline__ bool decide(Dec& d, bool greedy) {
+  __device__ __forceinline__ bool decide(Dec& d, bool greedy, int32_t x_act = -1, bool x_open = false) {
     PrioGuard<PART ? 0 : SFL_SETPRIO_DECIDE> prio;
     // PART: a row of this rank's own switches is decided in one pass, like the fused kernel
     const bool loc = local_sw((int)(trl(sdec, mctz(q_mask)) >> 16));
-    const bool observe_only = PART && !(flags & F_REQ) && !loc;
+    bool x_apply = false;
+    if constexpr (EXT) {
+      x_apply = x_open && x_act >= 0;
+      if (x_apply && x_act >= sw_rec((int)(trl(sdec, mctz(q_mask)) >> 16)).na()) {
+        lerr |= E_BAD_ACTION;
+        x_apply = false;
+      }
+    }
+    const bool observe_only = EXT ? !x_apply : (PART && !(flags & F_REQ) && !loc);
     // agent_iter: lowest queued train (switch_env.py:418-421, 616-622)
     // (PART observe pass: the observation needs one distance, looked up directly below; the
     // staging waits for the apply pass in the next launch)
@@ -1777,7 +1806,7 @@ struct WEnv {
     // pass's staging overlaps its state load; not kept.)
     if ((!pf_ok || (RING && pf_n >= PF_SLOTS)) && !observe_only) {
       prefetch(greedy);
-      pf_ok = !PART;  // (PART stages only this decision's train: the next one stages its own)
+      pf_ok = !PART && !EXT;  // (PART, EXT: only this decision's train is staged: the next one stages its own)
     }
     const int h = mctz(q_mask);
     if (!observe_only) mclear_low(q_mask);
@@ -1841,6 +1870,18 @@ struct WEnv {
     if constexpr (TM) {  // observe done (observer.py:246-308)
       if (tm_on) tm_obs_t = (uint64_t)__builtin_amdgcn_s_memtime();
     }
+    if constexpr (EXT) {
+      if (observe_only) {  // the observation of the queue's first train; the queue is left as it stands
+        d.sw = sw;
+        d.h = h;
+        d.slot = slot;
+        d.state = state;
+        d.amask = amask;
+        d.reward = slot_rew(U(ld(sbase(), slot_ix(sw, h))), epoch);
+        flags |= F_EXT_OBS;
+        return true;
+      }
+    }
     // issue the Q row load and the pending update's Q cell load, then draw while they fly
     const PortRec prr = port_rec(4 * sw + slot);
     const int w = prr.q_w();
@@ -1850,9 +1891,11 @@ struct WEnv {
     const bool colv = lid() < w;
     const bool row_hit = pf_roff_h == roff;  // the staged row and its greedy choice are valid
     double v_c = 0.0;
-    if (!row_hit && loc) v_c = ld(qbase() + roff, (size_t)(colv ? lid() : 0));
+    if constexpr (!EXT) {
+      if (!row_hit && loc) v_c = ld(qbase() + roff, (size_t)(colv ? lid() : 0));
+    }
     d.slotword = U(slot_v);
-    const uint32_t pend = greedy ? PEND_NONE : slot_pend(d.slotword, epoch);
+    const uint32_t pend = (EXT || greedy) ? PEND_NONE : slot_pend(d.slotword, epoch);
     d.qoff_pend = PF_NONE;
     double q_pend_v = 0.0;
     if (!observe_only && pend != PEND_NONE) {  // (observe pass: the LDS record was not staged)
@@ -1878,7 +1921,7 @@ struct WEnv {
     // epsilon-greedy
     int action = -1;
     bool explore = false;
-    if (!greedy && !xp::kNoRng) {
+    if (!EXT && !greedy && !xp::kNoRng) {
       // (kept in VGPRs: the 128-bit LCG runs on the vector ALU's 64-bit multiply-adds; the scalar
       // unit is the contended one)
       Pcg64 rng;
@@ -1953,7 +1996,10 @@ struct WEnv {
     // action a(c); every other action of the full row is default_q, the first of them at mind
     double mx;
     int best, arg;
-    if (PART && !loc) {
+    if constexpr (EXT) {  // the caller's action (in range: checked above)
+      mx = 0.0;
+      best = arg = x_act;
+    } else if (PART && !loc) {
       // the owner's reply: max over the full row, and the masked argmax (-1 for an exploratory request)
       best = arg = U((int)rep_a);
       mx = __longlong_as_double(((long long)U(rep_hi) << 32) | (long long)U(rep_lo));
@@ -2365,6 +2411,98 @@ struct WEnv {
     if (c.launch_ticks) st(c.launch_ticks, e, (uint64_t)ticks);
     if (c.launch_bytes) st(c.launch_bytes, e, (uint64_t)abytes);
   }
+
+  // ---- external-action mode (EXT): env_run_ext of sfl_core.h, operation for operation, for both drivers -------
+  // One launch = one call of sfl_env_step: the env applies the caller's action to the observation the last launch
+  // emitted, runs on to its next observation (or its episode's end) and stops there.  A flat loop like
+  // run_groups': an iteration advances the env by at most one reset, one tick, one post and one decision, so the
+  // groups of a wavefront (G < 64) tick together after their decisions; a group that has emitted leaves the loop
+  // while its wave-mates run on.  Ticks are not held back for deciding groups (SFL_TICK_HOLD): a launch holds at most
+  // two decisions per env.  Every output is written after the loop with plain vector stores: from the env's lane
+  // 0, the delays from the lanes that hold the trains.  Returns the phase to store.
+  __device__ __forceinline__ int32_t ext_run(const SflCtl& c, int32_t phase) {
+    const SflExt& x = *c.ext;
+    int32_t act = U(ld(x.actions, e));
+    int32_t o_next = -1, o_step = -1, o_trunc = 0;
+    bool applied = false, emitted = false;
+    uint32_t ticks = 0;
+    if (act == -2) {  // SFL_ACTION_RESET: the episode-end reset, where the env stands
+      phase = PH_RESET;
+      flags &= ~(F_EXT_OBS | F_INFLIGHT);
+      act = -1;
+    }
+    Dec d;
+    while (true) {
+      if (phase == PH_RESET) {
+        reset();
+        phase = PH_TICK;
+      }
+      if (phase == PH_TICK) {
+        tick();
+        ticks++;
+        phase = after_tick();
+      }
+      if (phase == PH_POST) {  // the step() of the applied action returns here (after the ticks when the queue emptied)
+        // the reward the train will see at the successor switch: the greedy post's only slot write
+        if (lid() == 0) st(sbase(), slot_ix(d.next_sw, d.h), slot_make(PEND_NONE, d.r_new, epoch));
+        flags &= ~F_INFLIGHT;
+        o_step = now;
+        ep_dec += 1;
+        n_dec += 1;
+        step_ctr += 1;
+        if ((int64_t)step_ctr > m.max_steps) flags |= F_TRUNC;
+        phase = after_post();
+      }
+      if (phase == PH_DECIDE) {
+        emitted = decide(d, true, act, (flags & F_EXT_OBS) != 0u && !applied);
+        if (emitted) break;
+        flags &= ~F_EXT_OBS;
+        flags |= F_INFLIGHT;
+        applied = true;
+        o_next = d.next_sw;
+        phase = many(q_mask) ? PH_POST : PH_TICK;  // no active switch left: move the trains first
+      }
+      if (phase == PH_END) {  // the caller records arrivals, delays, malfunctions
+        o_trunc = (flags & F_TRUNC) ? 1 : 0;
+        flags &= ~F_EXT_OBS;
+        phase = PH_RESET;
+        break;
+      }
+    }
+    // the episode's delays and malfunction count as they stand (its final values when agent == -1)
+#pragma unroll
+    for (int k = 0; k < TPL; ++k)
+      if (mine[k]) st(x.delays, (size_t)(lane + G * k) * E + e, delay[k]);
+    if (lid() == 0) {
+      st(x.agent, e, emitted ? (int32_t)d.sw : -1);
+      if (emitted) {
+        st(x.train, e, (int32_t)d.h);
+        st(x.slot, e, (int32_t)d.slot);
+        st(x.state, e, d.state);
+        st(x.mask, e, d.amask);
+        st(x.reward, e, d.reward);
+        st(x.now, e, now);
+      }
+      st(x.next_sw, e, o_next);
+      st(x.step_now, e, o_step);
+      st(x.n_mf, e, n_mf);
+      st(x.truncated, e, o_trunc);
+      uint64_t w[2];
+      if constexpr (TPL * G <= 64 || TWc <= 32) {
+        w[0] = arr_mask;
+        w[1] = 0ull;
+      } else {
+        w[0] = arr_mask.w[0];
+        w[1] = arr_mask.w[1];
+      }
+#pragma unroll
+      for (int j = 0; j < MAXW; ++j) st(x.arrived, (size_t)j * E + e, (uint32_t)(w[j >> 1] >> (32 * (j & 1))));
+      if (c.launch_dec) st(c.launch_dec, e, (uint64_t)(applied ? 1u : 0u));
+      if (c.launch_ticks) st(c.launch_ticks, e, (uint64_t)ticks);
+      if (c.launch_bytes) st(c.launch_bytes, e, (uint64_t)0);
+    }
+    return phase;
+  }
 };
 
 // driver: one env per wavefront until its episode target / decision budget (env_run in sfl_core.h)
@@ -2427,9 +2565,11 @@ struct PhaseTimer {
   }
 };
 
-template <int PPL, int SPL, int TW, bool TRACE, bool PART = false, bool TIMED = false, bool HPG = false>
+// EXT: one call of external-action mode (WEnv::ext_run; c.ext = the call's SflExt)
+template <int PPL, int SPL, int TW, bool TRACE, bool PART = false, bool TIMED = false, bool HPG = false, bool EXT = false>
 __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const SflPart* P = nullptr) {
-  using V = WEnv<PPL, SPL, TW, PART, 64, false, HPG>;
+  static_assert(!(EXT && (TRACE || TIMED)), "external-action mode: no trace, no phase timers");
+  using V = WEnv<PPL, SPL, TW, PART, 64, false, HPG, EXT>;
   // semaphores, counters, prefetch records, rng, timetable (PART: one record, timetable from the map)
   // (PART: the launch's initial records / counters in place of the timetable copy)
   constexpr int LDS_WORDS =
@@ -2448,6 +2588,10 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
   PhaseTimer tm;
   if constexpr (TIMED) tm.start(c.phase_cyc != nullptr && blockIdx.x % TM_SAMPLE == 0u);
   v.load();
+  if constexpr (EXT) {
+    v.store(v.ext_run(c, uni(ld(s.phase, e))));
+    return;
+  }
   if constexpr (PART)
     if (v.flags & F_DEFER) return;  // its records did not fit the last round's segments: it sits this one out
   if constexpr (xp::kLoadTwice) v.load();  // experiment build: the marginal cost of the state load
@@ -2572,9 +2716,10 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
 // follow it -- as a flat loop in which each iteration advances every group by at most one tick,
 // one post step and one decision.  The groups of a wave diverge (one ticks while another decides);
 // a batch loop as in run() would hold every group until the longest batch of the wave is done.
-template <int PPL, int SPL, int TW, bool TRACE, int G, bool TIMED = false, bool LM = false, bool HPG = false>
+template <int PPL, int SPL, int TW, bool TRACE, int G, bool TIMED = false, bool LM = false, bool HPG = false, bool EXT = false>
 __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) {
-  using V = WEnv<PPL, SPL, TW, false, G, LM, HPG>;
+  static_assert(!(EXT && (TRACE || TIMED)), "external-action mode: no trace, no phase timers");
+  using V = WEnv<PPL, SPL, TW, false, G, LM, HPG, EXT>;
   // per env: semaphores, counters, prefetch records, rng; per block: the timetable rows and the
   // per-switch / per-port map records (the groups of a wave read different switches' records: LDS
   // reads instead of vector loads)
@@ -2615,6 +2760,10 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
   PhaseTimer tm;
   if constexpr (TIMED) tm.start(c.phase_cyc != nullptr && blockIdx.x % TM_SAMPLE == 0u && threadIdx.x < 64u);
   v.load();
+  if constexpr (EXT) {
+    v.store(v.ext_run(c, ld(s.phase, e)));
+    return;
+  }
   int32_t phase = ld(s.phase, e);
   int32_t ep_t = ld(s.ep_t, e), n_test = ld(s.n_test, e);
   uint32_t ticks = 0, abytes = 0;

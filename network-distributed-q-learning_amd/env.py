@@ -43,13 +43,15 @@ class ASyncSwitchEnv:
     ``observer``: None or a ``StandardObserver`` (its ``delay_threshold`` reaches the kernels; see
     observer.py).  ``malfunction_stream="flatland"`` draws malfunctions in the order of Flatland's
     ``ParamMalfunctionGen`` on the reset-seeded ``np_random`` (mfstream.py) instead of the
-    counter-based stream of the frozen spec.
+    counter-based stream of the frozen spec.  ``env_kernel``: the AEC protocol's env step, ``"lane"``, ``"wave"`` or
+    None (``SFL_ENV_KERNEL``, default ``"lane"``): ``aec.AECBatch``'s ``kernel``.
     """
 
     def __init__(self, rail_env: Union[str, "mapgen.Scenario"], max_steps: int = 200, render_mode=None,
                  observer=None, seed: Optional[int] = None, n_envs: int = 1, device: int = 0,
-                 malfunction_stream: str = "counter"):
+                 malfunction_stream: str = "counter", env_kernel: Optional[str] = None):
         self.observer = observer
+        self.env_kernel = env_kernel
         self.delay_threshold = observer_mod.delay_threshold_of(observer)
         if isinstance(rail_env, str):
             sc = mapgen.make_config(rail_env) if rail_env in mapgen.CONFIGS else mapgen.Scenario.load(rail_env)
@@ -95,7 +97,8 @@ class ASyncSwitchEnv:
             if aec is not None:
                 aec.close()
             self._aec = AECBatch(self.compiled, [seed], lib=lib, device=self.device, max_steps=self.max_steps,
-                                 malfunction_stream=self.malfunction_stream, delay_threshold=self.delay_threshold)
+                                 malfunction_stream=self.malfunction_stream, delay_threshold=self.delay_threshold,
+                                 kernel=self.env_kernel)
             self._aec_seed = seed
             out = self._aec.step(None)
         else:

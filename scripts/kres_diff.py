@@ -1,7 +1,8 @@
 """Compare the wave kernels of two built libsfl.so files: VGPRs, SGPRs, spills, scratch, LDS and code size of every
 k_wave / k_wave2 / k_wave_g / k_wave_part / k_wave2_part instantiation, matched by shape (template arguments).  A
 trailing HPG = false argument (the hyperparameter-group switch, csrc/sfl_kwave_g.h) is dropped, so a library with it
-compares against one from before it; HPG = true kernels are listed on their own.  The "code" column says whether the
+compares against one from before it; HPG = true kernels are listed on their own.  Likewise the EXT argument behind it
+(external-action mode's kernels, sfl_env_begin_wave).  The "code" column says whether the
 kernel's machine code (the symbol's bytes in its code object's .text) is the same in both, or the same but for
 pc-relative addresses (same_code).  Exit status 1 if a kernel
 present in both differs in a resource field (registers, spills, scratch, LDS); code bytes alone do not fail.
@@ -65,10 +66,14 @@ def kernels_of(co):
             continue
         args = [("true" if v == "1" else "false") if t == "b" else v for t, v in re.findall(r"L([ib])(\d+)E", m.group(2))]
         full = {"k_wave": 6, "k_wave2": 6, "k_wave_g": 9}.get(m.group(1))  # (the part kernels have no HPG argument)
+        # (a trailing EXT argument behind HPG: external-action mode's kernels, listed on their own like HPG's)
+        ext = full is not None and len(args) == full + 1 and args[-1] == "true"
+        if full is not None and len(args) == full + 1:
+            args = args[:-1]
         hpg = len(args) == full and args[-1] == "true"
         if len(args) == full:
             args = args[:-1]
-        key = ("HPG " if hpg else "") + m.group(1) + "<" + ",".join(args) + ">"
+        key = ("EXT " if ext else "") + ("HPG " if hpg else "") + m.group(1) + "<" + ",".join(args) + ">"
         vals = [int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in FIELDS]
         out[key] = vals + [size.get(name, -1), code.get(name)]
     return out
