@@ -34,6 +34,10 @@
  *   sfl_env_step_dev / sfl_env_sync   the same protocol for a policy on the device: device pointers in and
  *                     out, the observation vector of observer.py:269-308 decoded on the device, queued on the
  *                     caller's stream without a wait (the one call that is not synchronous)
+ *   sfl_consensus / sfl_get_consensus_q   no counterpart in the reference, whose learners are one process each:
+ *                     the envs' Q-tables merged per cohort on the device (mean of the learned values, or the
+ *                     optimistic max of distributed Q-learning), handed back to every member, and one consensus
+ *                     table per cohort to evaluate and save (DistrQLearning.q_table / save of the merged learner)
  *   sfl_get_phase_cycles  the per-phase time accumulators            switchfl/switch_env.py:67-73
  *                     (flatland_step_time, last_time, action_selection_time, update_time, reset_time ...)
  */
@@ -338,6 +342,41 @@ typedef struct {
 #define SFL_MAX_HPARAM_GROUPS 4096
 int sfl_set_hparam_groups(sfl_handle* h, int32_t n_groups, const sfl_hparam_group* groups,
                           const uint16_t* env_group /* [n_envs] */);
+
+/* ---- consensus Q-tables: a cohort's learners merged on the device, and shared ----
+ * The envs of a handle are independent learners.  sfl_consensus merges their Q-tables per cohort -- env e belongs
+ * to cohort env_cohort[e] (SFL_NO_COHORT: to none; it is neither read nor written) -- into one consensus table and
+ * key set per cohort, which the handle keeps until the next call (sfl_get_consensus_q reads one), and with
+ * SFL_CONSENSUS_SHARE writes each cohort's result back into every member.  The rule, exact to the bit (host build,
+ * kernels and the test model agree), for cell i of row r of cohort c with members e_0 < e_1 < ...:
+ *   holders H: the members whose key-set bit r is set.  Consensus key set: bit r set iff H is not empty.
+ *   nobody holds r: the consensus cell is default_q, and SHARE writes no member's cells of that row.
+ *   MEAN: contributors C = the holders whose cell differs bitwise from default_q (an env that never updated a cell
+ *     does not pull it back toward the default).  C empty: default_q.  All contributors the same bit pattern: that
+ *     pattern, no arithmetic (Q-init values survive exactly; a second consensus of a shared cohort changes nothing).
+ *     Otherwise total / (double)|C|: the member list is cut by position into chunks of SFL_CONSENSUS_CHUNK, each
+ *     chunk's partial starts at +0.0 and adds its contributors in ascending env order, total starts at +0.0 and adds
+ *     the partials in ascending chunk order; no FMA.
+ *   MAX: over the holders H: the bit pattern of the lowest-indexed holder whose value no other holder exceeds
+ *     (compared with >, so -0.0 and +0.0 tie and the lower env wins).
+ *   SHARE: every member's cells of held rows become the consensus cells, its key set the OR of its own and the
+ *     consensus key set.  Nothing else of an env changes: its interaction counts (the epsilon / lr schedule
+ *     position), pending-update slots (they name cell indices), RNG and episode state stay its own.
+ * Synchronous, on the handle's stream (sfl_set_stream); kernel_ms (optional): the device time of the call's kernels
+ * (0 on the host build).  Refused: mode other than the two, unknown flag bits, n_cohorts == 0 or > n_envs, an
+ * env_cohort[e] that is neither < n_cohorts nor SFL_NO_COHORT, a graph-partitioned handle (its tables are owned
+ * rows), a handle in external-action mode (it has no learner); sfl_get_consensus_q also before any sfl_consensus and
+ * with cohort >= the last call's n_cohorts.  The consensus buffer is reallocated when n_cohorts changes. */
+#define SFL_CONSENSUS_MEAN  0
+#define SFL_CONSENSUS_MAX   1
+#define SFL_CONSENSUS_SHARE 1u            /* flags: write the result back into every member env */
+#define SFL_NO_COHORT       0xFFFFFFFFu   /* env_cohort[e]: env e takes no part and is never written */
+#define SFL_CONSENSUS_CHUNK 256           /* members per partial sum (fixes the arithmetic, above) */
+int sfl_consensus(sfl_handle* h, int32_t mode, uint32_t flags, uint32_t n_cohorts,
+                  const uint32_t* env_cohort /* [n_envs], NULL: every env in cohort 0 */,
+                  double* kernel_ms /* optional */);
+int sfl_get_consensus_q(sfl_handle* h, uint32_t cohort, double* q /* [q_per_env] */,
+                        uint32_t* touched /* [(rows+31)/32] */);
 #ifdef __cplusplus
 }
 #endif

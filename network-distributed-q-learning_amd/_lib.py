@@ -51,6 +51,11 @@ class HParamGroup(C.Structure):
 
 
 MAX_HPARAM_GROUPS = 4096  # include/sfl.h SFL_MAX_HPARAM_GROUPS
+# include/sfl.h SFL_CONSENSUS_*
+CONSENSUS_MODES = {"mean": 0, "max": 1}
+CONSENSUS_SHARE = 1
+NO_COHORT = 0xFFFFFFFF
+CONSENSUS_CHUNK = 256
 
 
 class RunArgs(C.Structure):
@@ -133,6 +138,9 @@ EXPORTS = {
     "sfl_part_get_q": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_double), P(C.c_uint32)]),
     # hyperparameter groups (runtime.Batch hparam_groups, sweep.py)
     "sfl_set_hparam_groups": (C.c_int, [C.c_void_p, C.c_int32, P(HParamGroup), P(C.c_uint16)]),
+    # consensus Q-tables (runtime.Batch consensus / consensus_raw)
+    "sfl_consensus": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_double)]),
+    "sfl_get_consensus_q": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_double), P(C.c_uint32)]),
 }
 
 

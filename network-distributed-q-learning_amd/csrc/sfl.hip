@@ -715,6 +715,23 @@ struct HipBackend {
     if (!check(hipGetLastError(), "k_env_encode launch")) return -1;
     return err.empty() ? 0 : -1;
   }
+  // sfl_consensus: the kernels of sfl_consensus.hip on the handle's stream, timed between the two events
+  static constexpr bool kConsPartials = true;
+  int consensus(const sfl::ConsArgs& a, float* ms) {
+    check(hipEventRecord(ev0, stream), "event");
+    const char* what = "";
+    int code = 0;
+    if (sfl::consensus_launch(a, (void*)stream, &what, &code)) {
+      if (err.empty()) err = std::string(what) + ": " + hipGetErrorString((hipError_t)code);
+      return -1;
+    }
+    check(hipEventRecord(ev1, stream), "event");
+    if (!check(event_wait(ev1), "sfl_consensus kernels")) return -1;
+    float t = 0.f;
+    hipEventElapsedTime(&t, ev0, ev1);
+    *ms = t;
+    return err.empty() ? 0 : -1;
+  }
   int sync() { return check(stream_wait(), "sync") && err.empty() ? 0 : -1; }
   // process-wide, one per device, built on first use and kept for the life of the process
   // SFL_SEEDSEQ_TABLE=0 (read on every call) runs without it, as a device that cannot hold its 8.6 GB does

@@ -299,4 +299,15 @@ int sfl_set_hparam_groups(sfl_handle* h, int32_t n_groups, const sfl_hparam_grou
   return sfl::set_hparam_groups(HH(h), n_groups, groups, env_group);
 }
 
+int sfl_consensus(sfl_handle* h, int32_t mode, uint32_t flags, uint32_t n_cohorts, const uint32_t* env_cohort,
+                  double* kernel_ms) {
+  if (!h) return sfl::fail("sfl_consensus: null handle");
+  return sfl::consensus(HH(h), mode, flags, n_cohorts, env_cohort, kernel_ms);
+}
+
+int sfl_get_consensus_q(sfl_handle* h, uint32_t cohort, double* q, uint32_t* touched) {
+  if (!h) return sfl::fail("sfl_get_consensus_q: null handle");
+  return sfl::get_consensus_q(HH(h), cohort, q, touched);
+}
+
 }  // extern "C"

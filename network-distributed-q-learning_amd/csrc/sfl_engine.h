@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/sfl.h"
+#include "sfl_consensus.h"
 #include "sfl_core.h"
 #include "sfl_mfgen.h"
 #include "sfl_part.h"
@@ -76,6 +77,12 @@ struct Handle {
   // per-phase cycles of the sampled wavefronts, accumulated over learn / test launches on the device
   // (sfl_get_phase_cycles reads them)
   uint64_t* d_phase = nullptr;
+  // consensus Q-tables (sfl_consensus): the tables [cons_n][q_per_env] and key sets [cons_n][touched_words] of the
+  // last call (cons_n == 0: none yet), and each cell's row id, built at the first call
+  double* cons_q = nullptr;
+  uint32_t* cons_keys = nullptr;
+  uint32_t cons_n = 0;
+  uint32_t* d_cell_row = nullptr;
 
   template <class T>
   T* dalloc(size_t n) {
@@ -1304,6 +1311,157 @@ int part_counts(Handle<B>* h, uint32_t* out, int32_t cap) {
   for (int32_t i = 0; i < n && i < cap; ++i) out[i] = i < (int32_t)h->part_counts.size() ? h->part_counts[i] : 0u;
   h->part_consumed = true;
   return 0;
+}
+
+// ---------------------------------------------------------------------------
+// consensus Q-tables (include/sfl.h sfl_consensus; sfl_consensus.h; DESIGN.md "Consensus Q-tables")
+// ---------------------------------------------------------------------------
+// Partial records (sum, first pattern, meta: 20 bytes a cell) exist only for the chunks of cohorts of more than
+// SFL_CONSENSUS_CHUNK members, at most 2 E / SFL_CONSENSUS_CHUNK chunks: the scratch is at most
+// 2 E / 256 * q_per_env * 20 bytes, 2 % of the Q block, allocated for the call and freed.
+template <class B>
+int consensus(Handle<B>* h, int32_t mode, uint32_t flags, uint32_t n_cohorts, const uint32_t* env_cohort, double* kernel_ms) {
+  if (mode != SFL_CONSENSUS_MEAN && mode != SFL_CONSENSUS_MAX)
+    return fail("sfl_consensus: mode " + std::to_string(mode) + " (SFL_CONSENSUS_MEAN or SFL_CONSENSUS_MAX)");
+  if (flags & ~(uint32_t)SFL_CONSENSUS_SHARE) return fail("sfl_consensus: unknown flag bits");
+  if (h->part.world) return fail("sfl_consensus: the handle is graph-partitioned (its tables are owned rows)");
+  if (h->env_mode) return fail("sfl_consensus: the handle is in external-action mode (no learner)");
+  const uint32_t E = h->E;
+  if (n_cohorts == 0 || n_cohorts > E)
+    return fail("sfl_consensus: n_cohorts " + std::to_string(n_cohorts) + " outside [1, n_envs = " + std::to_string(E) + "]");
+  if (env_cohort)
+    for (uint32_t e = 0; e < E; ++e)
+      if (env_cohort[e] >= n_cohorts && env_cohort[e] != SFL_NO_COHORT)
+        return fail("sfl_consensus: env " + std::to_string(e) + " is in cohort " + std::to_string(env_cohort[e]) + " of " +
+                    std::to_string(n_cohorts));
+  const SflMap& m = h->map;
+  const uint64_t Q = m.q_per_env;
+  const uint32_t tw = m.touched_words;
+  if (!h->d_cell_row) {
+    // each cell's row id, as k_qinit derives it: block g holds rows row_base[g] + state, q_w[g] cells each
+    std::vector<uint32_t> cr(Q ? Q : 1, CONS_NO_ROW);
+    for (int s = 0; s < m.S; ++s)
+      for (int i = 0; i < (int)h->h_sw_np[s]; ++i) {
+        const size_t g = (size_t)s * 4 + i;
+        const uint64_t w = h->h_q_w[g], nrows = ((uint64_t)1 << h->h_sw_np[s]) * (uint64_t)m.K * 3u;
+        if (w == 0) continue;
+        if (h->h_q_off[g] + nrows * w > Q || h->h_row_base[g] + nrows > m.rows_per_env)
+          return fail("sfl_consensus: a Q block lies outside the env's table (map compiler mismatch)");
+        for (uint64_t r = 0; r < nrows; ++r)
+          for (uint64_t j = 0; j < w; ++j) cr[h->h_q_off[g] + r * w + j] = h->h_row_base[g] + (uint32_t)r;
+      }
+    uint32_t* d = (uint32_t*)h->upload(cr.data(), cr.size());
+    if (!d || h->be.sync()) {
+      if (d) h->dfree(d);
+      return fail("sfl_consensus: device allocation failed (cell rows)");
+    }
+    h->d_cell_row = d;
+  }
+  if (h->cons_n != n_cohorts) {
+    if (h->cons_q) h->dfree(h->cons_q);
+    if (h->cons_keys) h->dfree(h->cons_keys);
+    h->cons_n = 0;
+    h->cons_q = h->template dalloc<double>((size_t)n_cohorts * Q);
+    h->cons_keys = h->template dalloc<uint32_t>((size_t)n_cohorts * tw);
+    if (!h->cons_q || !h->cons_keys) {
+      if (h->cons_q) h->dfree(h->cons_q);
+      if (h->cons_keys) h->dfree(h->cons_keys);
+      h->cons_q = nullptr;
+      h->cons_keys = nullptr;
+      return fail("sfl_consensus: device allocation failed (consensus tables)");
+    }
+  }
+  // member lists: the envs of each cohort in ascending order, cohort after cohort; their chunks as jobs
+  std::vector<uint32_t> off(n_cohorts + 1, 0u), members;
+  for (uint32_t e = 0; e < E; ++e) {
+    const uint32_t c = env_cohort ? env_cohort[e] : 0u;
+    if (c != SFL_NO_COHORT) ++off[c + 1];
+  }
+  for (uint32_t c = 0; c < n_cohorts; ++c) off[c + 1] += off[c];
+  members.resize(off[n_cohorts] ? off[n_cohorts] : 1);
+  {
+    std::vector<uint32_t> at(off.begin(), off.end() - 1);
+    for (uint32_t e = 0; e < E; ++e) {
+      const uint32_t c = env_cohort ? env_cohort[e] : 0u;
+      if (c != SFL_NO_COHORT) members[at[c]++] = e;
+    }
+  }
+  std::vector<ConsJob> jobs;
+  std::vector<ConsCombo> combos;
+  uint32_t n_slots = 0;
+  for (uint32_t c = 0; c < n_cohorts; ++c) {
+    const uint32_t n = off[c + 1] - off[c];
+    if (n <= SFL_CONSENSUS_CHUNK) {
+      jobs.push_back(ConsJob{off[c], n, c, CONS_DIRECT});
+      continue;
+    }
+    const uint32_t chunks = (n + SFL_CONSENSUS_CHUNK - 1) / SFL_CONSENSUS_CHUNK;
+    combos.push_back(ConsCombo{n_slots, chunks, c, 0u});
+    for (uint32_t k = 0; k < chunks; ++k) {
+      const uint32_t b = k * SFL_CONSENSUS_CHUNK;
+      jobs.push_back(ConsJob{off[c] + b, std::min<uint32_t>(SFL_CONSENSUS_CHUNK, n - b), c, n_slots++});
+    }
+  }
+  ConsArgs a{};
+  a.mode = mode;
+  a.flags = flags;
+  a.E = E;
+  a.n_cohorts = n_cohorts;
+  a.tw = tw;
+  a.n_jobs = (uint32_t)jobs.size();
+  a.n_combos = (uint32_t)combos.size();
+  a.n_slots = n_slots;
+  a.Q = Q;
+  a.default_bits = cons_bits(m.default_q);
+  const uint64_t q_tiles = (Q + CONS_TILE - 1) / CONS_TILE;
+  a.cells_cap = q_tiles * CONS_TILE;
+  a.q = h->st.q;
+  a.touched = h->st.touched;
+  a.cell_row = h->d_cell_row;
+  a.cons_q = h->cons_q;
+  a.cons_keys = h->cons_keys;
+  std::vector<void*> scratch;
+  auto up = [&](const void* src, size_t bytes) -> void* {
+    void* p = h->be.alloc(bytes ? bytes : 1);
+    scratch.push_back(p);
+    if (p && bytes && src) h->be.h2d(p, src, bytes);
+    return p;
+  };
+  a.members = (const uint32_t*)up(members.data(), members.size() * 4);
+  a.coh_off = (const uint32_t*)up(off.data(), off.size() * 4);
+  a.jobs = (const ConsJob*)up(jobs.data(), jobs.size() * sizeof(ConsJob));
+  a.combos = (const ConsCombo*)up(combos.data(), combos.size() * sizeof(ConsCombo));
+  if (n_slots && B::kConsPartials) {
+    const size_t recs = (size_t)n_slots * a.cells_cap;
+    a.p_sum = (double*)up(nullptr, recs * 8);
+    a.p_first = (uint64_t*)up(nullptr, recs * 8);
+    a.p_meta = (uint32_t*)up(nullptr, recs * 4);
+    a.p_keys = (uint32_t*)up(nullptr, (size_t)n_slots * tw * 4);
+  }
+  bool ok = true;
+  for (void* p : scratch) ok = ok && p;
+  float ms = 0.f;
+  int rc = ok ? h->be.consensus(a, &ms) : -1;
+  if (h->be.sync()) rc = -1;  // (the host sources of the uploads live until here)
+  for (void* p : scratch) h->be.free(p);
+  if (!ok) return fail("sfl_consensus: device allocation failed (member lists or partial records)");
+  if (rc) return fail(std::string("sfl_consensus: ") + h->be.error());
+  h->cons_n = n_cohorts;
+  if (kernel_ms) *kernel_ms = ms;
+  return 0;
+}
+
+template <class B>
+int get_consensus_q(Handle<B>* h, uint32_t cohort, double* q, uint32_t* touched) {
+  if (h->part.world) return fail("sfl_get_consensus_q: the handle is graph-partitioned");
+  if (h->env_mode) return fail("sfl_get_consensus_q: the handle is in external-action mode (no learner)");
+  if (!h->cons_n) return fail("sfl_get_consensus_q: no sfl_consensus call yet");
+  if (cohort >= h->cons_n)
+    return fail("sfl_get_consensus_q: cohort " + std::to_string(cohort) + " of " + std::to_string(h->cons_n));
+  const size_t Q = h->map.q_per_env, tw = h->map.touched_words;
+  if (q) h->be.d2h(q, h->cons_q + (size_t)cohort * Q, Q * 8);
+  if (touched) h->be.d2h(touched, h->cons_keys + (size_t)cohort * tw, tw * 4);
+  return h->be.sync() ? fail(h->be.error()) : 0;
 }
 
 }  // namespace sfl

@@ -80,6 +80,13 @@ struct HostBackend {
     for (int64_t t = 0; t < n; ++t) sfl::env_encode_item(enc, (uint32_t)t);
     return 0;
   }
+  // sfl_consensus: the rule as plain loops (sfl_consensus.h), no partial records
+  static constexpr bool kConsPartials = false;
+  int consensus(const sfl::ConsArgs& a, float* ms) {
+    sfl::consensus_host(a);
+    *ms = 0.f;
+    return 0;
+  }
   int sync() { return 0; }
   uint64_t n_wait = 0;  // (nothing to wait for: the host build runs on the caller's thread)
   const uint32_t* seedseq_table() { return nullptr; }  // the host build draws every sub-generator

@@ -237,10 +237,27 @@ class DistrQLearning:
         self._timing(t0)
         return cum, arrived, delays
 
-    def save(self, filename: str, mode: str = "pickle", envs: Optional[Sequence[int]] = None):
-        """distr_q.py:492-508 — pickle of the Q dict (a list of dicts for a batch); ``envs``: of those envs only."""
+    def consensus_table(self, mode: str = "mean", cohorts: Optional[Sequence[Optional[int]]] = None,
+                        share: bool = False) -> Dict[tuple, list]:
+        """The envs' Q-tables merged on the device (runtime.Batch.consensus: "mean" or "max"; ``cohorts[e]`` env e's
+        cohort or None, default one cohort of every env) -- cohort 0's consensus table as the reference's dict.
+        ``share=True`` also writes each cohort's table back into its members."""
+        self.batch.consensus(mode, cohorts, share=share)
+        return self.batch.consensus_dict(0)
+
+    def save(self, filename: str, mode: str = "pickle", envs: Optional[Sequence[int]] = None,
+             consensus: Optional[str] = None):
+        """distr_q.py:492-508 — pickle of the Q dict (a list of dicts for a batch); ``envs``: of those envs only.
+        ``consensus`` ("mean" / "max"): one dict instead, the consensus table of those envs (of every env by default)
+        as one cohort, merged without changing any env -- the file a single reference learner would have saved."""
         if mode != "pickle":
             raise NotImplementedError("only mode='pickle' is supported (the reference defines no csv/parquet dumper)")
+        if consensus is not None:
+            member = None if envs is None else set(int(e) for e in envs)
+            cohorts = None if member is None else [0 if e in member else None for e in range(self.batch.E)]
+            with open(filename, "wb") as f:
+                pickle.dump(self.consensus_table(consensus, cohorts, share=False), f)
+            return
         envs = range(self.batch.E) if envs is None else envs
         obj = self.batch.q_dict(envs[0]) if len(envs) == 1 else [self.batch.q_dict(e) for e in envs]
         with open(filename, "wb") as f:

@@ -29,6 +29,34 @@ def numpy_rng_state(seed: int) -> List[int]:
     return [s >> 64, s & m, inc >> 64, inc & m, (int(st["has_uint32"]) << 32) | int(st["uinteger"])]
 
 
+def raw_to_dict(cm: CompiledMap, default_q: float, q: np.ndarray, touched: np.ndarray) -> Dict[tuple, list]:
+    """A compact Q block and key-set bitmap (the layout of Batch.q_raw) as the reference's ``q_table`` dict:
+    touched rows as {observation tuple: [Q per action]}."""
+    bits = np.unpackbits(touched.view(np.uint8), bitorder="little")[:cm.rows_per_env]
+    rows = np.nonzero(bits)[0]
+    A = cm.arrays
+    dq = float(default_q)
+    out = {}
+    for s in range(cm.S):
+        for slot in range(len(cm.ports[s])):
+            g = 4 * s + slot
+            base, nrows = int(A["row_base"][g]), (1 << len(cm.ports[s])) * cm.K * 3
+            sel = rows[(rows >= base) & (rows < base + nrows)]
+            if len(sel) == 0:
+                continue
+            w = int(A["q_w"][g])
+            off = int(A["q_off"][g])
+            routes = [a for a, (src, _) in enumerate(cm.outcomes[s]) if src == slot] + [int(cm.n_actions[s]) - 1]
+            for r in sel:
+                stt = int(r) - base
+                vals = q[off + stt * w: off + (stt + 1) * w]
+                full = [dq] * int(cm.n_actions[s])
+                for j, a in enumerate(routes):
+                    full[a] = float(vals[j])
+                out[cm.obs_of_row(s, slot, stt)] = full
+    return out
+
+
 class Batch:
     """Owns one device handle.  ``hp`` uses the reference's DistrQLearning argument names."""
 
@@ -293,31 +321,64 @@ class Batch:
 
     def q_dict(self, env: int) -> Dict[tuple, list]:
         """Touched rows as {observation tuple: [Q per action]} — the reference's ``q_table``."""
-        cm = self.cm
-        q, touched = self.q_raw(env)
-        bits = np.unpackbits(touched.view(np.uint8), bitorder="little")[:cm.rows_per_env]
-        rows = np.nonzero(bits)[0]
-        A = cm.arrays
-        dq = float(self.hp["default_q"])
-        out = {}
-        for s in range(cm.S):
-            for slot in range(len(cm.ports[s])):
-                g = 4 * s + slot
-                base, nrows = int(A["row_base"][g]), (1 << len(cm.ports[s])) * cm.K * 3
-                sel = rows[(rows >= base) & (rows < base + nrows)]
-                if len(sel) == 0:
-                    continue
-                w = int(A["q_w"][g])
-                off = int(A["q_off"][g])
-                routes = [a for a, (src, _) in enumerate(cm.outcomes[s]) if src == slot] + [int(cm.n_actions[s]) - 1]
-                for r in sel:
-                    stt = int(r) - base
-                    vals = q[off + stt * w: off + (stt + 1) * w]
-                    full = [dq] * int(cm.n_actions[s])
-                    for j, a in enumerate(routes):
-                        full[a] = float(vals[j])
-                    out[cm.obs_of_row(s, slot, stt)] = full
-        return out
+        return raw_to_dict(self.cm, self.hp["default_q"], *self.q_raw(env))
+
+    # ---- consensus Q-tables (sfl_consensus): a cohort's learners merged on the device, and shared ----
+    def consensus(self, mode: str = "mean", cohorts: Optional[Sequence[Optional[int]]] = None,
+                  share: bool = True, n_cohorts: Optional[int] = None) -> float:
+        """Merge the envs' Q-tables per cohort (include/sfl.h sfl_consensus): ``mode`` "mean" (of the learned values)
+        or "max" (the optimistic merge of distributed Q-learning); ``cohorts[e]`` is env e's cohort id, ``None`` for
+        an env that takes no part (default: every env in cohort 0); ``share`` writes each cohort's table back into
+        its members; ``n_cohorts`` (default: the highest id + 1) may name more cohorts than have members (their
+        table is ``default_q``, their key set empty).  The handle keeps the consensus tables (``consensus_raw`` /
+        ``consensus_dict``).  Returns the kernel ms."""
+        if mode not in _lib.CONSENSUS_MODES:
+            raise ValueError(f"consensus: mode {mode!r} (one of {sorted(_lib.CONSENSUS_MODES)})")
+        ms = C.c_double(0.0)
+        if cohorts is None:
+            n, ptr = 1, None
+        else:
+            if len(cohorts) != self.E:
+                raise ValueError(f"consensus: cohorts must name a cohort (or None) for each of the {self.E} envs")
+            ids = [_lib.NO_COHORT if c is None else int(c) for c in cohorts]
+            if min(ids) < 0 or max(ids) > _lib.NO_COHORT:
+                raise ValueError("consensus: cohort ids must be non-negative")
+            arr = np.array(ids, dtype=np.uint32)
+            n = max([c + 1 for c in ids if c != _lib.NO_COHORT], default=1)
+            ptr = _ptr(arr, C.c_uint32)
+        n = n if n_cohorts is None else int(n_cohorts)
+        self.lib.check(self.lib.dll.sfl_consensus(self.h, _lib.CONSENSUS_MODES[mode],
+                                                  _lib.CONSENSUS_SHARE if share else 0, n, ptr, C.byref(ms)),
+                       "sfl_consensus")
+        return float(ms.value)
+
+    def consensus_raw(self, cohort: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """The consensus table and key set of one cohort of the last ``consensus`` call, in the layout of q_raw."""
+        q = np.zeros(self.cm.q_per_env)
+        t = np.zeros((self.cm.rows_per_env + 31) // 32, np.uint32)
+        self.lib.check(self.lib.dll.sfl_get_consensus_q(self.h, int(cohort), _ptr(q, C.c_double), _ptr(t, C.c_uint32)),
+                       "sfl_get_consensus_q")
+        return q, t
+
+    def consensus_dict(self, cohort: int = 0) -> Dict[tuple, list]:
+        """One cohort's consensus table as the reference's ``q_table`` dict (the format of q_dict)."""
+        return raw_to_dict(self.cm, self.hp["default_q"], *self.consensus_raw(cohort))
+
+    def step_shared(self, decisions_per_env: int, sync_every: int, mode: str = "mean",
+                    cohorts: Optional[Sequence[Optional[int]]] = None) -> Tuple[int, float, float]:
+        """``decisions_per_env`` learning decisions per env in rounds of ``step(sync_every)`` (the last one shorter),
+        each followed by ``consensus(mode, cohorts, share=True)``.  Returns (total decisions, step kernel ms,
+        consensus kernel ms)."""
+        if decisions_per_env <= 0 or sync_every <= 0:
+            raise ValueError("step_shared: decisions_per_env and sync_every must be positive")
+        total, step_ms, cons_ms, left = 0, 0.0, 0.0, int(decisions_per_env)
+        while left > 0:
+            n, ms = self.step(min(int(sync_every), left))
+            left -= min(int(sync_every), left)
+            total += n
+            step_ms += ms
+            cons_ms += self.consensus(mode, cohorts, share=True)
+        return total, step_ms, cons_ms
 
     def load_q_dict(self, env: int, table: Dict[tuple, list]):
         """Inverse of ``q_dict`` (``DistrQLearning.load``); rejects rows the compact layout cannot hold."""
