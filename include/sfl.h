@@ -38,6 +38,9 @@
  *                     the envs' Q-tables merged per cohort on the device (mean of the learned values, or the
  *                     optimistic max of distributed Q-learning), handed back to every member, and one consensus
  *                     table per cohort to evaluate and save (DistrQLearning.q_table / save of the merged learner)
+ *   sfl_curve_begin / sfl_curve_read   the per-episode record learn() returns (cum_reward, arrived_trains,
+ *                     num_malfunctions, delays: distr_q.py:346-366) for sfl_step, reduced on the device into
+ *                     learning curves per episode bin and env series instead of [episode][env] host arrays
  *   sfl_get_phase_cycles  the per-phase time accumulators            switchfl/switch_env.py:67-73
  *                     (flatland_step_time, last_time, action_selection_time, update_time, reset_time ...)
  */
@@ -377,6 +380,60 @@ int sfl_consensus(sfl_handle* h, int32_t mode, uint32_t flags, uint32_t n_cohort
                   double* kernel_ms /* optional */);
 int sfl_get_consensus_q(sfl_handle* h, uint32_t cohort, double* q /* [q_per_env] */,
                         uint32_t* touched /* [(rows+31)/32] */);
+
+/* ---- step-mode learning curves: the episodes sfl_step ends, reduced on the device ----
+ * sfl_step reports decisions only; the per-episode record of the reference's learn() (cum_reward, arrived_trains,
+ * num_malfunctions, delays: distr_q.py:346-366) exists through sfl_learn alone, as [episode][env] host arrays.  A
+ * curve keeps that record for step mode at any batch size: the handle owns a device ring of ring_cap statistics rows
+ * per env (the rows every kernel writes at an episode's end, row = episode index % ring_cap), and after every
+ * successful sfl_step launch a fold kernel reduces the rows the launch wrote into a table of n_bins x n_series cells.
+ *   Bins: episode i of an env (its learning-episode index since sfl_learn_begin, 0-based) falls in bin
+ *     min(i / bin_episodes, n_bins - 1): the last bin collects everything beyond.
+ *   Series: env e belongs to series env_series[e] < n_series.  With env_series == NULL on a handle with
+ *     hyperparameter groups it is the env's group at the time of the call, and n_series must equal the group count;
+ *     with NULL on any other handle it is 0.
+ *   Empty cells (count == 0): the min fields are INT64_MAX, the max fields INT64_MIN, first_episode INT64_MAX and
+ *     last_episode -1.  `lost` alone may be non-zero in such a cell.
+ *   Fold, after each launch, for env e with mark b (the episodes accounted for so far) and a = its episode index
+ *     now: the episodes max(b, a - ring_cap) .. a - 1 are folded from ring rows i % ring_cap into their cells; the
+ *     episodes b .. max(b, a - ring_cap) - 1, whose rows were overwritten, add 1 to `lost` of their own cell and to
+ *     nothing else; the mark becomes a.  A launch of D decisions per env ends at most D + 1 episodes of an env
+ *     whose episodes make a decision each (the one the previous launch's last decision finished, then one per
+ *     decision at the most), so with ring_cap >= D + 1 nothing is lost; an episode in which no train reaches a
+ *     switch makes no decision and is the one way past that bound.  Every field is an integer (cum_reward is an
+ *     exact integer in its double), so the table does not depend on the order in which envs are folded.
+ *   sfl_curve_begin starts a curve (replacing the handle's curve if it has one): cells empty, every env's mark at
+ *     its current episode index (0 right after sfl_learn_begin).  sfl_learn_begin on a handle with a curve zeroes
+ *     the marks and empties the cells.  sfl_learn and sfl_test neither record nor fold (their own buffers receive
+ *     the rows, as without a curve); after sfl_learn the marks are set to the envs' episode indices, so a later
+ *     sfl_step folds only its own episodes.  A handle without a curve runs sfl_step exactly as before.
+ *   sfl_curve_read copies the table, [n_bins][n_series] cells; sfl_curve_episodes the marks (per env: the episode
+ *     index up to which its learning episodes are accounted for -- folded, lost, or ended before the curve began);
+ *     sfl_curve_fold_ms the device time of the last fold and of all folds since sfl_curve_begin (0 on the host
+ *     build; never part of sfl_counters.last_kernel_ms or sfl_step's kernel_ms); sfl_curve_end frees everything.
+ * Refused: bin_episodes, n_bins, n_series or ring_cap below 1, an env_series[e] >= n_series, n_series other than
+ * the group count (NULL series on a grouped handle), a graph-partitioned handle, a handle in external-action mode,
+ * a table above SFL_CURVE_MAX_TABLE_BYTES or a ring (ring_cap * n_envs * (24 + 4 T) bytes) above
+ * SFL_CURVE_MAX_RING_BYTES; read / episodes / end on a handle without a curve. */
+typedef struct {            /* one (bin, series) cell: 16 x int64, 128 bytes */
+  int64_t count;            /* episodes folded */
+  int64_t lost;             /* episodes that ended but were overwritten in the ring before the fold */
+  int64_t arrived_sum, arrived_min, arrived_max;
+  int64_t all_arrived;      /* episodes with arrived == T */
+  int64_t reward_sum, reward_min, reward_max;   /* cum_reward, an exact integer */
+  int64_t decisions_sum, ticks_sum, malfunctions_sum;
+  int64_t delay_sum;        /* sum over the episode's T trains of their delays */
+  int64_t truncated;        /* episodes with decisions > max_steps */
+  int64_t first_episode, last_episode;          /* lowest / highest episode index folded */
+} sfl_curve_cell;
+#define SFL_CURVE_MAX_TABLE_BYTES (64ull << 20)
+#define SFL_CURVE_MAX_RING_BYTES  (1ull << 30)
+int sfl_curve_begin(sfl_handle* h, int32_t bin_episodes, int32_t n_bins, uint32_t n_series,
+                    const uint32_t* env_series /* [n_envs] or NULL */, int32_t ring_cap);
+int sfl_curve_read(sfl_handle* h, sfl_curve_cell* out /* [n_bins][n_series] */);
+int sfl_curve_episodes(sfl_handle* h, int32_t* out /* [n_envs] */);
+int sfl_curve_fold_ms(sfl_handle* h, double* last_ms, double* total_ms /* either may be NULL */);
+int sfl_curve_end(sfl_handle* h);
 #ifdef __cplusplus
 }
 #endif

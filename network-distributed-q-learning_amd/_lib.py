@@ -56,6 +56,12 @@ CONSENSUS_MODES = {"mean": 0, "max": 1}
 CONSENSUS_SHARE = 1
 NO_COHORT = 0xFFFFFFFF
 CONSENSUS_CHUNK = 256
+# include/sfl.h sfl_curve_cell: the 16 int64 words of a cell in order, and SFL_CURVE_MAX_*
+CURVE_FIELDS = ("count", "lost", "arrived_sum", "arrived_min", "arrived_max", "all_arrived", "reward_sum", "reward_min",
+                "reward_max", "decisions_sum", "ticks_sum", "malfunctions_sum", "delay_sum", "truncated", "first_episode",
+                "last_episode")
+CURVE_MAX_TABLE_BYTES = 64 << 20
+CURVE_MAX_RING_BYTES = 1 << 30
 
 
 class RunArgs(C.Structure):
@@ -141,6 +147,12 @@ EXPORTS = {
     # consensus Q-tables (runtime.Batch consensus / consensus_raw)
     "sfl_consensus": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_double)]),
     "sfl_get_consensus_q": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_double), P(C.c_uint32)]),
+    # step-mode learning curves (runtime.Batch curve_begin / curve / curve_end)
+    "sfl_curve_begin": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, P(C.c_uint32), C.c_int32]),
+    "sfl_curve_read": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "sfl_curve_episodes": (C.c_int, [C.c_void_p, P(C.c_int32)]),
+    "sfl_curve_fold_ms": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double)]),
+    "sfl_curve_end": (C.c_int, [C.c_void_p]),
 }
 
 

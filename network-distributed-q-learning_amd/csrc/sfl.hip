@@ -732,6 +732,19 @@ struct HipBackend {
     *ms = t;
     return err.empty() ? 0 : -1;
   }
+  // sfl_curve_*: k_curve_fold of sfl_curve.hip queued on the handle's stream between the two events (elapsed_ms()
+  // after the caller's sync is the fold's time), or k_curve_reset
+  int curve(const sfl::CurveArgs& a, bool reset) {
+    if (!reset) check(hipEventRecord(ev0, stream), "event");
+    const char* what = "";
+    int code = 0;
+    if (sfl::curve_launch(a, reset, (void*)stream, &what, &code)) {
+      if (err.empty()) err = std::string(what) + ": " + hipGetErrorString((hipError_t)code);
+      return -1;
+    }
+    if (!reset) check(hipEventRecord(ev1, stream), "event");
+    return err.empty() ? 0 : -1;
+  }
   int sync() { return check(stream_wait(), "sync") && err.empty() ? 0 : -1; }
   // process-wide, one per device, built on first use and kept for the life of the process
   // SFL_SEEDSEQ_TABLE=0 (read on every call) runs without it, as a device that cannot hold its 8.6 GB does

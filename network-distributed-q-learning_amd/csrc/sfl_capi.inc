@@ -71,6 +71,7 @@ int sfl_learn(sfl_handle* h, sfl_run_args* args) {
   c.dec_budget = 0;
   int rc = sfl::run(hh, c, args);
   if (rc == 0) rc = count_launch(hh);
+  if (rc == 0) rc = sfl::curve_skip_to_now(hh);
   return rc;
 }
 
@@ -308,6 +309,35 @@ int sfl_consensus(sfl_handle* h, int32_t mode, uint32_t flags, uint32_t n_cohort
 int sfl_get_consensus_q(sfl_handle* h, uint32_t cohort, double* q, uint32_t* touched) {
   if (!h) return sfl::fail("sfl_get_consensus_q: null handle");
   return sfl::get_consensus_q(HH(h), cohort, q, touched);
+}
+
+int sfl_curve_begin(sfl_handle* h, int32_t bin_episodes, int32_t n_bins, uint32_t n_series, const uint32_t* env_series,
+                    int32_t ring_cap) {
+  if (!h) return sfl::fail("sfl_curve_begin: null handle");
+  return sfl::curve_begin(HH(h), bin_episodes, n_bins, n_series, env_series, ring_cap);
+}
+
+int sfl_curve_read(sfl_handle* h, sfl_curve_cell* out) {
+  if (!h) return sfl::fail("sfl_curve_read: null handle");
+  return sfl::curve_read(HH(h), out);
+}
+
+int sfl_curve_episodes(sfl_handle* h, int32_t* out) {
+  if (!h) return sfl::fail("sfl_curve_episodes: null handle");
+  return sfl::curve_episodes(HH(h), out);
+}
+
+int sfl_curve_fold_ms(sfl_handle* h, double* last_ms, double* total_ms) {
+  if (!h) return sfl::fail("sfl_curve_fold_ms: null handle");
+  if (!HH(h)->cv.on) return sfl::fail("sfl_curve_fold_ms: the handle has no curve (sfl_curve_begin)");
+  if (last_ms) *last_ms = HH(h)->cv.last_ms;
+  if (total_ms) *total_ms = HH(h)->cv.total_ms;
+  return 0;
+}
+
+int sfl_curve_end(sfl_handle* h) {
+  if (!h) return sfl::fail("sfl_curve_end: null handle");
+  return sfl::curve_end(HH(h));
 }
 
 }  // extern "C"

@@ -1,0 +1,96 @@
+// Step-mode learning curves (include/sfl.h sfl_curve_*): the cell layout, the work description both backends take, and
+// the host build's plain loops.  The rule is stated once, in include/sfl.h and DESIGN.md §17; curve_fold_host below, the
+// kernel of sfl_curve.hip and the test model (tests/_curve.py) are three implementations of it that agree exactly.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/sfl.h"
+
+namespace sfl {
+
+// a cell as 16 int64 words, in the order of sfl_curve_cell
+enum {
+  CV_COUNT = 0, CV_LOST, CV_ARR_SUM, CV_ARR_MIN, CV_ARR_MAX, CV_ALL_ARR, CV_REW_SUM, CV_REW_MIN, CV_REW_MAX,
+  CV_DEC_SUM, CV_TICK_SUM, CV_MF_SUM, CV_DELAY_SUM, CV_TRUNC, CV_EP_FIRST, CV_EP_LAST, CV_WORDS
+};
+static_assert(sizeof(sfl_curve_cell) == CV_WORDS * 8, "sfl_curve_cell is 16 int64 words");
+
+struct CurveArgs {
+  uint32_t E, n_series;
+  int32_t T, n_bins, bin_episodes, ring_cap;
+  int64_t max_steps;            // an episode is truncated when its decisions exceed it
+  const int32_t* ep_t;          // [E] the envs' learning-episode indices
+  int32_t* mark;                // [E] episodes accounted for so far
+  const uint32_t* series;       // [E]
+  const double* st_cum;         // the ring: [ring_cap][E] ...
+  const int32_t* st_arrived;
+  const int32_t* st_mf;
+  const int32_t* st_dec;
+  const int32_t* st_ticks;
+  const int32_t* st_delays;     // ... and [ring_cap][T][E]
+  int64_t* cells;               // [n_bins][n_series][CV_WORDS]
+};
+
+#if defined(__HIPCC__)
+#define SFL_CV_FN __host__ __device__ inline
+#else
+#define SFL_CV_FN inline
+#endif
+
+SFL_CV_FN size_t curve_cell_of(const CurveArgs& a, int32_t episode, uint32_t series) {
+  int32_t bin = episode / a.bin_episodes;
+  if (bin > a.n_bins - 1) bin = a.n_bins - 1;
+  return (size_t)bin * a.n_series + series;
+}
+
+SFL_CV_FN void curve_cell_clear(int64_t* c) {
+  for (int k = 0; k < CV_WORDS; ++k) c[k] = 0;
+  c[CV_ARR_MIN] = c[CV_REW_MIN] = c[CV_EP_FIRST] = INT64_MAX;
+  c[CV_ARR_MAX] = c[CV_REW_MAX] = INT64_MIN;
+  c[CV_EP_LAST] = -1;
+}
+
+// The host build: the rule as written, one env, one episode at a time ("device" memory is host memory here).
+inline void curve_reset_host(const CurveArgs& a) {
+  for (size_t c = 0; c < (size_t)a.n_bins * a.n_series; ++c) curve_cell_clear(a.cells + c * CV_WORDS);
+}
+
+inline void curve_fold_host(const CurveArgs& a) {
+  const size_t E = a.E;
+  for (uint32_t e = 0; e < a.E; ++e) {
+    const int32_t end = a.ep_t[e], b = a.mark[e];
+    const int32_t kept = end - a.ring_cap > b ? end - a.ring_cap : b;
+    for (int32_t i = b; i < kept; ++i) a.cells[curve_cell_of(a, i, a.series[e]) * CV_WORDS + CV_LOST] += 1;
+    for (int32_t i = kept; i < end; ++i) {
+      int64_t* c = a.cells + curve_cell_of(a, i, a.series[e]) * CV_WORDS;
+      const size_t row = (size_t)(i % a.ring_cap);
+      const int64_t arrived = a.st_arrived[row * E + e], reward = (int64_t)a.st_cum[row * E + e];
+      const int64_t dec = a.st_dec[row * E + e];
+      int64_t delay = 0;
+      for (int32_t h = 0; h < a.T; ++h) delay += a.st_delays[(row * (size_t)a.T + h) * E + e];
+      c[CV_COUNT] += 1;
+      c[CV_ARR_SUM] += arrived;
+      if (arrived < c[CV_ARR_MIN]) c[CV_ARR_MIN] = arrived;
+      if (arrived > c[CV_ARR_MAX]) c[CV_ARR_MAX] = arrived;
+      c[CV_ALL_ARR] += arrived == a.T ? 1 : 0;
+      c[CV_REW_SUM] += reward;
+      if (reward < c[CV_REW_MIN]) c[CV_REW_MIN] = reward;
+      if (reward > c[CV_REW_MAX]) c[CV_REW_MAX] = reward;
+      c[CV_DEC_SUM] += dec;
+      c[CV_TICK_SUM] += a.st_ticks[row * E + e];
+      c[CV_MF_SUM] += a.st_mf[row * E + e];
+      c[CV_DELAY_SUM] += delay;
+      c[CV_TRUNC] += dec > a.max_steps ? 1 : 0;
+      if (i < c[CV_EP_FIRST]) c[CV_EP_FIRST] = i;
+      if (i > c[CV_EP_LAST]) c[CV_EP_LAST] = i;
+    }
+    a.mark[e] = end;
+  }
+}
+
+// sfl_curve.hip: queues one kernel on `stream` (a hipStream_t) -- the fold, or with `reset` the kernel that empties the
+// cells; 0, or -1 with the failing launch's name in *what and HIP's error code in *code
+int curve_launch(const CurveArgs& a, bool reset, void* stream, const char** what, int* code);
+
+}  // namespace sfl

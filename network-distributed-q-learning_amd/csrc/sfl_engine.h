@@ -16,6 +16,7 @@
 #include "../../include/sfl.h"
 #include "sfl_consensus.h"
 #include "sfl_core.h"
+#include "sfl_curve.h"
 #include "sfl_mfgen.h"
 #include "sfl_part.h"
 
@@ -83,6 +84,14 @@ struct Handle {
   uint32_t* cons_keys = nullptr;
   uint32_t cons_n = 0;
   uint32_t* d_cell_row = nullptr;
+  // step-mode learning curve (sfl_curve_*; sfl_curve.h): the ring the kernels write at episode ends, the marks, the
+  // series ids and the cells, all in cv.a; the device time of the last fold and of all folds since sfl_curve_begin
+  struct Curve {
+    bool on = false;
+    CurveArgs a{};
+    float last_ms = 0.f;
+    double total_ms = 0.0;
+  } cv;
 
   template <class T>
   T* dalloc(size_t n) {
@@ -624,6 +633,10 @@ int learn_begin(Handle<B>* h, const uint64_t* rng_states) {
   h->be.d2h(fl.data(), h->st.eflags, E * 4);
   for (auto& f : fl) f &= ~(F_EXPLOIT_DONE | F_INFLIGHT | F_GREEDY);
   h->be.h2d(h->st.eflags, fl.data(), E * 4);
+  if (h->cv.on) {  // the curve starts over with the episode indices: marks at 0, cells empty
+    h->be.memset(h->cv.a.mark, 0, E * 4);
+    if (h->be.curve(h->cv.a, true)) return fail(std::string("sfl_learn_begin: ") + h->be.error());
+  }
   return h->be.sync() ? fail(h->be.error()) : 0;
 }
 
@@ -761,6 +774,20 @@ int run(Handle<B>* h, const SflCtl& c_in, sfl_run_args* args) {
     h->be.memset(c.sx_cum, 0, (size_t)cap * E * 8);
     h->be.memset(c.sx_arrived, 0, (size_t)cap * E * 4);
   }
+  // sfl_step on a handle with a curve: the episode-end rows go to the handle's ring (row = episode index % ring_cap),
+  // folded behind the launch; sfl_learn / sfl_test (args) keep their own buffers
+  const bool curve = !args && h->cv.on;
+  if (curve) {
+    const CurveArgs& a = h->cv.a;
+    c.stats_cap = a.ring_cap;
+    c.stats_base = 0;
+    c.st_cum = const_cast<double*>(a.st_cum);
+    c.st_arrived = const_cast<int32_t*>(a.st_arrived);
+    c.st_mf = const_cast<int32_t*>(a.st_mf);
+    c.st_dec = const_cast<int32_t*>(a.st_dec);
+    c.st_ticks = const_cast<int32_t*>(a.st_ticks);
+    c.st_delays = const_cast<int32_t*>(a.st_delays);
+  }
   c.launch_dec = h->d_launch_dec;
   c.launch_ticks = h->d_launch_ticks;
   c.launch_bytes = h->d_launch_bytes;
@@ -783,6 +810,7 @@ int run(Handle<B>* h, const SflCtl& c_in, sfl_run_args* args) {
   float ms = 0.f;
   int rc = h->be.run(h->map, h->st, c, h->variant, &ms);
   h->last_kernel_ms = ms;
+  if (!rc && curve) rc = h->be.curve(h->cv.a, false);  // (timed on its own: elapsed_ms after the sync below)
   if (!rc && args && cap > 0) {
     if (args->cum_reward) h->be.d2h(args->cum_reward, c.st_cum, (size_t)cap * E * 8);
     if (args->arrived) h->be.d2h(args->arrived, c.st_arrived, (size_t)cap * E * 4);
@@ -800,6 +828,10 @@ int run(Handle<B>* h, const SflCtl& c_in, sfl_run_args* args) {
   if (!rc) rc = h->be.sync();
   for (void* p : scratch) h->be.free(p);
   if (rc) return fail(std::string("sfl_run: ") + h->be.error());
+  if (curve) {
+    h->cv.last_ms = h->be.elapsed_ms();
+    h->cv.total_ms += h->cv.last_ms;
+  }
   return check_errors(h);
 }
 
@@ -1461,6 +1493,124 @@ int get_consensus_q(Handle<B>* h, uint32_t cohort, double* q, uint32_t* touched)
   const size_t Q = h->map.q_per_env, tw = h->map.touched_words;
   if (q) h->be.d2h(q, h->cons_q + (size_t)cohort * Q, Q * 8);
   if (touched) h->be.d2h(touched, h->cons_keys + (size_t)cohort * tw, tw * 4);
+  return h->be.sync() ? fail(h->be.error()) : 0;
+}
+
+// ---------------------------------------------------------------------------
+// step-mode learning curves (include/sfl.h sfl_curve_*; sfl_curve.h)
+// ---------------------------------------------------------------------------
+template <class B>
+int curve_end(Handle<B>* h) {
+  if (!h->cv.on) return fail("sfl_curve_end: the handle has no curve (sfl_curve_begin)");
+  if (h->be.sync()) return fail(h->be.error());
+  const CurveArgs& a = h->cv.a;
+  for (const void* p : {(const void*)a.mark, (const void*)a.series, (const void*)a.st_cum, (const void*)a.st_arrived,
+                        (const void*)a.st_mf, (const void*)a.st_dec, (const void*)a.st_ticks, (const void*)a.st_delays,
+                        (const void*)a.cells})
+    if (p) h->dfree((void*)p);
+  h->cv = typename Handle<B>::Curve{};
+  return 0;
+}
+
+template <class B>
+int curve_begin(Handle<B>* h, int32_t bin_episodes, int32_t n_bins, uint32_t n_series, const uint32_t* env_series,
+                int32_t ring_cap) {
+  if (h->part.world) return fail("sfl_curve_begin: the handle is graph-partitioned (sfl_part_local records no episodes)");
+  if (h->env_mode) return fail("sfl_curve_begin: the handle is in external-action mode (sfl_env_begin): no sfl_step to fold");
+  if (bin_episodes < 1 || n_bins < 1 || n_series < 1 || ring_cap < 1)
+    return fail("sfl_curve_begin: bin_episodes, n_bins, n_series and ring_cap must be at least 1");
+  const size_t E = h->E, T = (size_t)h->map.T;
+  const uint64_t table_bytes = (uint64_t)n_bins * n_series * sizeof(sfl_curve_cell);
+  if (table_bytes > SFL_CURVE_MAX_TABLE_BYTES)
+    return fail("sfl_curve_begin: n_bins * n_series cells take " + std::to_string(table_bytes) + " bytes, above " +
+                std::to_string(SFL_CURVE_MAX_TABLE_BYTES) + " (SFL_CURVE_MAX_TABLE_BYTES)");
+  const uint64_t ring_bytes = (uint64_t)ring_cap * E * (24 + 4 * T);
+  if (ring_bytes > SFL_CURVE_MAX_RING_BYTES)
+    return fail("sfl_curve_begin: a ring of " + std::to_string(ring_cap) + " rows takes " + std::to_string(ring_bytes) +
+                " bytes, above " + std::to_string(SFL_CURVE_MAX_RING_BYTES) + " (SFL_CURVE_MAX_RING_BYTES)");
+  std::vector<uint32_t> ser(E, 0u);
+  if (env_series) {
+    for (size_t e = 0; e < E; ++e) {
+      if (env_series[e] >= n_series)
+        return fail("sfl_curve_begin: env " + std::to_string(e) + " is in series " + std::to_string(env_series[e]) + " of " +
+                    std::to_string(n_series));
+      ser[e] = env_series[e];
+    }
+  } else if (h->map.env_group) {
+    if (n_series != (uint32_t)h->map.n_groups)
+      return fail("sfl_curve_begin: n_series " + std::to_string(n_series) + " is not the handle's group count " +
+                  std::to_string(h->map.n_groups) + " (env_series == NULL takes each env's hyperparameter group)");
+    std::vector<uint16_t> eg(E);
+    h->be.d2h(eg.data(), h->map.env_group, E * 2);
+    if (h->be.sync()) return fail(h->be.error());
+    for (size_t e = 0; e < E; ++e) ser[e] = eg[e];
+  }
+  if (h->cv.on)
+    if (int rc = curve_end(h)) return rc;
+  CurveArgs a{};
+  a.E = h->E;
+  a.n_series = n_series;
+  a.T = h->map.T;
+  a.n_bins = n_bins;
+  a.bin_episodes = bin_episodes;
+  a.ring_cap = ring_cap;
+  a.max_steps = h->map.max_steps;
+  a.ep_t = h->st.ep_t;
+  const size_t R = (size_t)ring_cap;
+  a.mark = h->template dalloc<int32_t>(E);
+  a.series = h->template dalloc<uint32_t>(E);
+  a.st_cum = h->template dalloc<double>(R * E);
+  a.st_arrived = h->template dalloc<int32_t>(R * E);
+  a.st_mf = h->template dalloc<int32_t>(R * E);
+  a.st_dec = h->template dalloc<int32_t>(R * E);
+  a.st_ticks = h->template dalloc<int32_t>(R * E);
+  a.st_delays = h->template dalloc<int32_t>(R * T * E);
+  a.cells = h->template dalloc<int64_t>((size_t)n_bins * n_series * CV_WORDS);
+  h->cv.a = a;
+  h->cv.on = true;  // (curve_end releases whatever was allocated)
+  if (!a.mark || !a.series || !a.st_cum || !a.st_arrived || !a.st_mf || !a.st_dec || !a.st_ticks || !a.st_delays || !a.cells) {
+    curve_end(h);
+    return fail("sfl_curve_begin: device allocation failed (ring or cells)");
+  }
+  h->be.h2d((void*)a.series, ser.data(), E * 4);
+  h->be.d2d(a.mark, h->st.ep_t, E * 4);  // the episodes before the curve are neither folded nor lost
+  h->be.memset((void*)a.st_cum, 0, R * E * 8);
+  h->be.memset((void*)a.st_arrived, 0, R * E * 4);
+  h->be.memset((void*)a.st_mf, 0, R * E * 4);
+  h->be.memset((void*)a.st_dec, 0, R * E * 4);
+  h->be.memset((void*)a.st_ticks, 0, R * E * 4);
+  h->be.memset((void*)a.st_delays, 0, R * T * E * 4);
+  int rc = h->be.curve(a, true);
+  if (h->be.sync()) rc = -1;  // (the host source of the series upload lives until here)
+  if (rc) {
+    curve_end(h);
+    return fail(std::string("sfl_curve_begin: ") + h->be.error());
+  }
+  return 0;
+}
+
+template <class B>
+int curve_read(Handle<B>* h, sfl_curve_cell* out) {
+  if (!h->cv.on) return fail("sfl_curve_read: the handle has no curve (sfl_curve_begin)");
+  if (!out) return fail("sfl_curve_read: null argument");
+  const CurveArgs& a = h->cv.a;
+  h->be.d2h(out, a.cells, (size_t)a.n_bins * a.n_series * sizeof(sfl_curve_cell));
+  return h->be.sync() ? fail(h->be.error()) : 0;
+}
+
+template <class B>
+int curve_episodes(Handle<B>* h, int32_t* out) {
+  if (!h->cv.on) return fail("sfl_curve_episodes: the handle has no curve (sfl_curve_begin)");
+  if (!out) return fail("sfl_curve_episodes: null argument");
+  h->be.d2h(out, h->cv.a.mark, (size_t)h->E * 4);
+  return h->be.sync() ? fail(h->be.error()) : 0;
+}
+
+// after sfl_learn: its episodes went to its own buffers; a later sfl_step folds only its own
+template <class B>
+int curve_skip_to_now(Handle<B>* h) {
+  if (!h->cv.on) return 0;
+  h->be.d2d(h->cv.a.mark, h->st.ep_t, (size_t)h->E * 4);
   return h->be.sync() ? fail(h->be.error()) : 0;
 }
 

@@ -87,6 +87,12 @@ struct HostBackend {
     *ms = 0.f;
     return 0;
   }
+  // sfl_curve_*: the fold (or the cells' reset) as plain loops (sfl_curve.h)
+  int curve(const sfl::CurveArgs& a, bool reset) {
+    if (reset) sfl::curve_reset_host(a);
+    else sfl::curve_fold_host(a);
+    return 0;
+  }
   int sync() { return 0; }
   uint64_t n_wait = 0;  // (nothing to wait for: the host build runs on the caller's thread)
   const uint32_t* seedseq_table() { return nullptr; }  // the host build draws every sub-generator

@@ -280,8 +280,91 @@ class Batch:
         """Advance every env by ``decisions_per_env`` learning decisions; returns (total decisions, kernel ms)."""
         n = C.c_uint64(0)
         ms = C.c_double(0.0)
-        self.lib.check(self.lib.dll.sfl_step(self.h, int(decisions_per_env), C.byref(n), C.byref(ms)), "sfl_step")
+        d = int(decisions_per_env)
+        self._largest_step = max(getattr(self, "_largest_step", 0), d)
+        ring = getattr(self, "_curve_ring", None)
+        if ring is not None and d + 1 > ring and not self._curve_warned:
+            import warnings
+            self._curve_warned = True
+            warnings.warn(f"step({d}) may end up to {d + 1} episodes per env, more than the curve's ring of {ring} rows: "
+                          f"the overwritten ones are counted in `lost` (curve_begin(ring={d + 1}) keeps them all)",
+                          RuntimeWarning, stacklevel=2)
+        self.lib.check(self.lib.dll.sfl_step(self.h, d, C.byref(n), C.byref(ms)), "sfl_step")
         return int(n.value), float(ms.value)
+
+    # ---- step-mode learning curves (sfl_curve_*): the episodes step() ends, reduced on the device ----
+    def curve_ring_max(self) -> int:
+        """The most ring rows sfl_curve_begin accepts for this batch (SFL_CURVE_MAX_RING_BYTES)."""
+        return max(1, _lib.CURVE_MAX_RING_BYTES // (self.E * (24 + 4 * self.cm.T)))
+
+    def curve_begin(self, bin_episodes: int, n_bins: int, series: Optional[Sequence[int]] = None,
+                    n_series: Optional[int] = None, ring: Optional[int] = None) -> int:
+        """Start recording learning curves in step mode (include/sfl.h sfl_curve_begin): from now on every ``step``
+        folds the episodes it ended into a table of ``n_bins`` x ``n_series`` cells -- episode i of an env in bin
+        min(i // bin_episodes, n_bins - 1), env e in series ``series[e]``.  ``series=None``: each env's hyperparameter
+        group on a batch that has groups (``n_series`` defaults to the group count), else series 0.  ``n_series``
+        defaults to the highest id + 1.  ``ring``: statistics rows kept per env between folds; a ``step(D)`` ends at
+        most D + 1 episodes per env, so ``ring >= D + 1`` loses none.  ``ring=None`` picks min(D + 1, the most rows
+        ``curve_ring_max()`` allows) with D the largest ``step`` this batch has run so far, or 64 if it has run none;
+        a later ``step(D)`` with D + 1 > ring warns once.  Returns the ring size.  Replaces a running curve."""
+        if series is None:
+            ptr = None
+            n = len(self.hparam_groups) or 1
+        else:
+            if len(series) != self.E:
+                raise ValueError(f"curve_begin: series must name a series for each of the {self.E} envs")
+            ids = [int(s) for s in series]
+            if min(ids) < 0 or max(ids) > 0xFFFFFFFF:
+                raise ValueError("curve_begin: series ids must be non-negative")
+            arr = np.array(ids, dtype=np.uint32)
+            ptr = _ptr(arr, C.c_uint32)
+            n = max(ids) + 1
+        n = n if n_series is None else int(n_series)
+        if ring is None:
+            ring = min((getattr(self, "_largest_step", 0) or 64) + 1, self.curve_ring_max())
+        self.lib.check(self.lib.dll.sfl_curve_begin(self.h, int(bin_episodes), int(n_bins), n, ptr, int(ring)),
+                       "sfl_curve_begin")
+        self._curve_shape = (int(n_bins), n)
+        self._curve_ring = int(ring)
+        self._curve_warned = False
+        return int(ring)
+
+    def curve(self) -> Dict[str, np.ndarray]:
+        """The curve so far: one int64 array [n_bins][n_series] per field of sfl_curve_cell (``_lib.CURVE_FIELDS``);
+        ``episodes`` [E], each env's learning episodes accounted for (folded or lost); and the float means
+        ``arrived_mean``, ``reward_mean``, ``decisions_per_episode``, ``ticks_per_decision``, ``truncated_frac`` and
+        ``all_arrived_frac`` over the folded episodes of each cell, NaN where ``count == 0``."""
+        if getattr(self, "_curve_shape", None) is None:
+            raise _lib.SflError("curve: no curve on this batch (curve_begin)")
+        nb, ns = self._curve_shape
+        cells = np.zeros((nb, ns, len(_lib.CURVE_FIELDS)), np.int64)
+        self.lib.check(self.lib.dll.sfl_curve_read(self.h, _ptr(cells, C.c_int64)), "sfl_curve_read")
+        ep = np.zeros(self.E, np.int32)
+        self.lib.check(self.lib.dll.sfl_curve_episodes(self.h, _ptr(ep, C.c_int32)), "sfl_curve_episodes")
+        out = {k: np.ascontiguousarray(cells[:, :, i]) for i, k in enumerate(_lib.CURVE_FIELDS)}
+        out["episodes"] = ep
+        cnt = out["count"].astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            per_ep = lambda k: np.where(cnt > 0, out[k] / cnt, np.nan)  # noqa: E731
+            out["arrived_mean"] = per_ep("arrived_sum")
+            out["reward_mean"] = per_ep("reward_sum")
+            out["decisions_per_episode"] = per_ep("decisions_sum")
+            out["truncated_frac"] = per_ep("truncated")
+            out["all_arrived_frac"] = per_ep("all_arrived")
+            out["ticks_per_decision"] = np.where((cnt > 0) & (out["decisions_sum"] > 0),
+                                                 out["ticks_sum"] / out["decisions_sum"].astype(np.float64), np.nan)
+        return out
+
+    def curve_fold_ms(self) -> Tuple[float, float]:
+        """Device ms of the last fold and of all folds since ``curve_begin`` (never part of ``step``'s kernel ms)."""
+        last, total = C.c_double(0.0), C.c_double(0.0)
+        self.lib.check(self.lib.dll.sfl_curve_fold_ms(self.h, C.byref(last), C.byref(total)), "sfl_curve_fold_ms")
+        return float(last.value), float(total.value)
+
+    def curve_end(self) -> None:
+        """Stop recording and free the ring and the table: ``step`` runs as on a batch that never had a curve."""
+        self.lib.check(self.lib.dll.sfl_curve_end(self.h), "sfl_curve_end")
+        self._curve_shape = self._curve_ring = None
 
     PHASES = ("tick", "observe", "egreedy", "apply", "post", "reset", "other")
 
