@@ -434,6 +434,54 @@ int sfl_curve_read(sfl_handle* h, sfl_curve_cell* out /* [n_bins][n_series] */);
 int sfl_curve_episodes(sfl_handle* h, int32_t* out /* [n_envs] */);
 int sfl_curve_fold_ms(sfl_handle* h, double* last_ms, double* total_ms /* either may be NULL */);
 int sfl_curve_end(sfl_handle* h);
+
+/* ---- the exploit record of a curve: the greedy rounds sfl_step runs, folded on the device ----
+ * The reference judges a learner by its exploit rounds: before learning episode t with (t + 1) % exploit_freq == 0 it
+ * runs one greedy episode (distr_q.py:278-281).  sfl_curve_exploit(h, f) with f >= 1 makes every later sfl_step launch
+ * with exploit_freq = f -- the kernels then walk the trajectory of sfl_learn with that frequency, a decision budget
+ * that runs out inside a round resumes in it -- and record each round's cum_reward and arrived trains in two more
+ * arrays of the curve's ring, [ring_cap][n_envs] double and int32 (row = t % ring_cap; 12 more bytes per row and env).
+ * Behind the curve's fold a second kernel folds the rounds into a table of n_bins x n_series exploit cells, with the
+ * curve's bins and series.  All arithmetic is integer:
+ *   Rounds: round r (0-based) of an env precedes episode t_r = (r + 1) * f - 1.  An env at episode index a whose
+ *     flags word says "exploit round done" (x) has completed n = a / f + ((x && (a + 1) % f == 0) ? 1 : 0) rounds.
+ *   Period: p = ring_cap / gcd(ring_cap, f); rounds r and r + p share a ring row.
+ *   Fold, after each launch, for env e with mark b (the rounds accounted for so far): the rounds max(b, n - p) .. n - 1
+ *     are folded from ring rows t_r % ring_cap into cell (min(t_r / bin_episodes, n_bins - 1), series[e]): count += 1,
+ *     the arrived fields from the row's arrived trains, all_arrived += (arrived == T), the reward fields from
+ *     (int64)cum_reward, first_episode / last_episode from t_r.  The rounds b .. max(b, n - p) - 1 add 1 to `lost` of
+ *     their own cell and to nothing else.  The mark becomes n.  With ring_cap coprime to f, p = ring_cap, and a launch
+ *     of D decisions per env with ring_cap >= D + 1 loses no round.
+ *   Empty cells are as in sfl_curve_cell: min fields INT64_MAX, max fields INT64_MIN, first_episode INT64_MAX,
+ *     last_episode -1.
+ *   sfl_curve_exploit with f >= 1 needs a curve; the first such call allocates the record; every such call empties the
+ *     exploit cells and sets each env's mark to the rounds it has completed under f by now.  f == 0: no new round
+ *     starts; a round in flight is finished by the kernels (the env's greedy flag holds until its next reset) and
+ *     folded, no other round is counted from then on, and the cells stay readable (on a curve without a record the
+ *     call does nothing).  sfl_curve_begin on a handle with an exploit record drops it with the curve it replaces;
+ *     sfl_curve_end frees it.  sfl_learn_begin empties the cells and zeroes the marks.  sfl_learn and sfl_test neither
+ *     record nor fold into it; after sfl_learn and after sfl_mark_exploit_done (which sets the done flag without a
+ *     row having been written) the marks are set to the rounds completed now.  A handle on which sfl_curve_exploit
+ *     is never called runs sfl_step with exploit_freq = 0 and folds exactly as before.
+ *   Not the reference's: with f == 1 an env standing at episode 0 runs its first round on the initialised Q-table
+ *     (learn() runs it before __init_q_table, distr_q.py:278-300).  Greedy decisions count towards sfl_step's decisions
+ *     per env and the handle's counters, as in sfl_learn.
+ *   sfl_curve_read_exploit copies the cells, [n_bins][n_series]; sfl_curve_rounds the marks, [n_envs].  The exploit
+ *     fold's device time is part of what sfl_curve_fold_ms reports; sfl_curve_exploit_fold_ms reports it alone.
+ * Refused: f < 0; a handle without a curve; a ring whose bytes with the two arrays, ring_cap * n_envs * (36 + 4 T),
+ * exceed SFL_CURVE_MAX_RING_BYTES; read_exploit / rounds / exploit_fold_ms on a handle without an exploit record. */
+typedef struct {            /* one (bin, series) exploit cell: 11 x int64 */
+  int64_t count;            /* rounds folded */
+  int64_t lost;             /* rounds that ended but were overwritten in the ring before the fold */
+  int64_t arrived_sum, arrived_min, arrived_max;
+  int64_t all_arrived;      /* rounds with arrived == T */
+  int64_t reward_sum, reward_min, reward_max;   /* cum_reward, an exact integer */
+  int64_t first_episode, last_episode;          /* lowest / highest episode index t a folded round preceded */
+} sfl_curve_xcell;
+int sfl_curve_exploit(sfl_handle* h, int32_t exploit_freq);
+int sfl_curve_read_exploit(sfl_handle* h, sfl_curve_xcell* out /* [n_bins][n_series] */);
+int sfl_curve_rounds(sfl_handle* h, int32_t* out /* [n_envs] */);
+int sfl_curve_exploit_fold_ms(sfl_handle* h, double* last_ms, double* total_ms /* either may be NULL */);
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,9 @@ CONSENSUS_CHUNK = 256
 CURVE_FIELDS = ("count", "lost", "arrived_sum", "arrived_min", "arrived_max", "all_arrived", "reward_sum", "reward_min",
                 "reward_max", "decisions_sum", "ticks_sum", "malfunctions_sum", "delay_sum", "truncated", "first_episode",
                 "last_episode")
+# include/sfl.h sfl_curve_xcell: the 11 int64 words of an exploit cell in order
+CURVE_XFIELDS = ("count", "lost", "arrived_sum", "arrived_min", "arrived_max", "all_arrived", "reward_sum", "reward_min",
+                 "reward_max", "first_episode", "last_episode")
 CURVE_MAX_TABLE_BYTES = 64 << 20
 CURVE_MAX_RING_BYTES = 1 << 30
 
@@ -153,6 +156,11 @@ EXPORTS = {
     "sfl_curve_episodes": (C.c_int, [C.c_void_p, P(C.c_int32)]),
     "sfl_curve_fold_ms": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double)]),
     "sfl_curve_end": (C.c_int, [C.c_void_p]),
+    # the curve's exploit record (runtime.Batch curve_begin(exploit_freq=) / curve_exploit)
+    "sfl_curve_exploit": (C.c_int, [C.c_void_p, C.c_int32]),
+    "sfl_curve_read_exploit": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "sfl_curve_rounds": (C.c_int, [C.c_void_p, P(C.c_int32)]),
+    "sfl_curve_exploit_fold_ms": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double)]),
 }
 
 

@@ -530,6 +530,7 @@ struct HipBackend {
   hipStream_t stream = nullptr;      // the stream every call of the handle queues on
   hipStream_t own_stream = nullptr;  // the handle's own (stream unless sfl_set_stream chose the caller's)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t ev2 = nullptr;  // behind the exploit fold (curve_exploit), created with the first one
   void* d_params = nullptr;  // device copies of SflMap | SflState | SflCtl
   std::string err;
   int dev = 0;
@@ -563,6 +564,7 @@ struct HipBackend {
   ~HipBackend() {
     if (ev0) hipEventDestroy(ev0);
     if (ev1) hipEventDestroy(ev1);
+    if (ev2) hipEventDestroy(ev2);
     if (d_params) hipFree(d_params);
     if (d_pparams) hipFree(d_pparams);
     if (d_eparams) hipFree(d_eparams);
@@ -744,6 +746,25 @@ struct HipBackend {
     }
     if (!reset) check(hipEventRecord(ev1, stream), "event");
     return err.empty() ? 0 : -1;
+  }
+  // sfl_curve_exploit: k_curve_fold_exploit of sfl_curve.hip queued behind curve()'s fold, with an event of its own
+  // behind it (elapsed_exploit_ms() after the caller's sync: from the fold's end to the exploit fold's), or the kernel
+  // that empties the exploit cells
+  int curve_exploit(const sfl::CurveXArgs& a, bool reset) {
+    if (!ev2 && !check(hipEventCreate(&ev2), "hipEventCreate")) return -1;
+    const char* what = "";
+    int code = 0;
+    if (sfl::curve_xlaunch(a, reset, (void*)stream, &what, &code)) {
+      if (err.empty()) err = std::string(what) + ": " + hipGetErrorString((hipError_t)code);
+      return -1;
+    }
+    if (!reset) check(hipEventRecord(ev2, stream), "event");
+    return err.empty() ? 0 : -1;
+  }
+  float elapsed_exploit_ms() {
+    float t = 0.f;
+    hipEventElapsedTime(&t, ev1, ev2);
+    return t;
   }
   int sync() { return check(stream_wait(), "sync") && err.empty() ? 0 : -1; }
   // process-wide, one per device, built on first use and kept for the life of the process

@@ -98,7 +98,7 @@ int sfl_step(sfl_handle* h, int64_t decisions_per_env, uint64_t* decisions_done,
   H* hh = HH(h);
   sfl::SflCtl c{};
   c.mode = 0;
-  c.exploit_freq = 0;
+  c.exploit_freq = hh->cv.x_on ? hh->cv.x_freq : 0;  // greedy rounds only with an exploit record (sfl_curve_exploit)
   c.ep_target = -1;
   c.dec_budget = decisions_per_env;
   int rc = sfl::run(hh, c, nullptr);
@@ -332,6 +332,29 @@ int sfl_curve_fold_ms(sfl_handle* h, double* last_ms, double* total_ms) {
   if (!HH(h)->cv.on) return sfl::fail("sfl_curve_fold_ms: the handle has no curve (sfl_curve_begin)");
   if (last_ms) *last_ms = HH(h)->cv.last_ms;
   if (total_ms) *total_ms = HH(h)->cv.total_ms;
+  return 0;
+}
+
+int sfl_curve_exploit(sfl_handle* h, int32_t exploit_freq) {
+  if (!h) return sfl::fail("sfl_curve_exploit: null handle");
+  return sfl::curve_exploit(HH(h), exploit_freq);
+}
+
+int sfl_curve_read_exploit(sfl_handle* h, sfl_curve_xcell* out) {
+  if (!h) return sfl::fail("sfl_curve_read_exploit: null handle");
+  return sfl::curve_read_exploit(HH(h), out);
+}
+
+int sfl_curve_rounds(sfl_handle* h, int32_t* out) {
+  if (!h) return sfl::fail("sfl_curve_rounds: null handle");
+  return sfl::curve_rounds(HH(h), out);
+}
+
+int sfl_curve_exploit_fold_ms(sfl_handle* h, double* last_ms, double* total_ms) {
+  if (!h) return sfl::fail("sfl_curve_exploit_fold_ms: null handle");
+  if (!HH(h)->cv.x_on) return sfl::fail("sfl_curve_exploit_fold_ms: the handle has no exploit record (sfl_curve_exploit)");
+  if (last_ms) *last_ms = HH(h)->cv.x_last_ms;
+  if (total_ms) *total_ms = HH(h)->cv.x_total_ms;
   return 0;
 }
 

@@ -89,8 +89,88 @@ inline void curve_fold_host(const CurveArgs& a) {
   }
 }
 
+// ---- the exploit record (include/sfl.h sfl_curve_exploit): the greedy rounds sfl_step runs ----
+// an exploit cell as 11 int64 words, in the order of sfl_curve_xcell
+enum {
+  XV_COUNT = 0, XV_LOST, XV_ARR_SUM, XV_ARR_MIN, XV_ARR_MAX, XV_ALL_ARR, XV_REW_SUM, XV_REW_MIN, XV_REW_MAX, XV_EP_FIRST,
+  XV_EP_LAST, XV_WORDS
+};
+static_assert(sizeof(sfl_curve_xcell) == XV_WORDS * 8, "sfl_curve_xcell is 11 int64 words");
+constexpr uint32_t CVX_DONE = 8u;  // F_EXPLOIT_DONE of the env's flags word (sfl_core.h; sfl_engine.h asserts it)
+
+struct CurveXArgs {
+  uint32_t E, n_series;
+  int32_t T, n_bins, bin_episodes, ring_cap;
+  int32_t f;                    // the frequency the rounds are counted with (the last sfl_curve_exploit with f >= 1)
+  int32_t period;               // ring_cap / gcd(ring_cap, f): rounds r and r + period share a ring row
+  const int32_t* ep_t;          // [E]
+  const uint32_t* eflags;       // [E] the envs' flags words
+  int32_t* mark;                // [E] rounds accounted for so far
+  const int32_t* limit;         // [E] after sfl_curve_exploit(h, 0): the rounds an env can still complete; else null
+  const uint32_t* series;       // [E] (the curve's)
+  const double* sx_cum;         // the ring: [ring_cap][E]
+  const int32_t* sx_arrived;
+  int64_t* cells;               // [n_bins][n_series][XV_WORDS]
+};
+
+// the rounds an env at episode index a with flags word `flags` has completed under frequency f
+SFL_CV_FN int32_t curve_rounds_done(int32_t a, uint32_t flags, int32_t f) {
+  return a / f + (((flags & CVX_DONE) && (a + 1) % f == 0) ? 1 : 0);
+}
+
+// the episode round r precedes (never above the env's episode index, so it fits an int32)
+SFL_CV_FN int32_t curve_round_episode(int32_t r, int32_t f) { return (int32_t)(((int64_t)r + 1) * f - 1); }
+
+SFL_CV_FN size_t curve_xcell_of(const CurveXArgs& a, int32_t episode, uint32_t series) {
+  int32_t bin = episode / a.bin_episodes;
+  if (bin > a.n_bins - 1) bin = a.n_bins - 1;
+  return (size_t)bin * a.n_series + series;
+}
+
+SFL_CV_FN void curve_xcell_clear(int64_t* c) {
+  for (int k = 0; k < XV_WORDS; ++k) c[k] = 0;
+  c[XV_ARR_MIN] = c[XV_REW_MIN] = c[XV_EP_FIRST] = INT64_MAX;
+  c[XV_ARR_MAX] = c[XV_REW_MAX] = INT64_MIN;
+  c[XV_EP_LAST] = -1;
+}
+
+inline void curve_xreset_host(const CurveXArgs& a) {
+  for (size_t c = 0; c < (size_t)a.n_bins * a.n_series; ++c) curve_xcell_clear(a.cells + c * XV_WORDS);
+}
+
+inline void curve_xfold_host(const CurveXArgs& a) {
+  const size_t E = a.E;
+  for (uint32_t e = 0; e < a.E; ++e) {
+    int32_t n = curve_rounds_done(a.ep_t[e], a.eflags[e], a.f);
+    if (a.limit && a.limit[e] < n) n = a.limit[e];
+    const int32_t b = a.mark[e];
+    const int32_t kept = n - a.period > b ? n - a.period : b;
+    for (int32_t r = b; r < kept; ++r)
+      a.cells[curve_xcell_of(a, curve_round_episode(r, a.f), a.series[e]) * XV_WORDS + XV_LOST] += 1;
+    for (int32_t r = kept; r < n; ++r) {
+      const int32_t t = curve_round_episode(r, a.f);
+      int64_t* c = a.cells + curve_xcell_of(a, t, a.series[e]) * XV_WORDS;
+      const size_t row = (size_t)(t % a.ring_cap);
+      const int64_t arrived = a.sx_arrived[row * E + e], reward = (int64_t)a.sx_cum[row * E + e];
+      c[XV_COUNT] += 1;
+      c[XV_ARR_SUM] += arrived;
+      if (arrived < c[XV_ARR_MIN]) c[XV_ARR_MIN] = arrived;
+      if (arrived > c[XV_ARR_MAX]) c[XV_ARR_MAX] = arrived;
+      c[XV_ALL_ARR] += arrived == a.T ? 1 : 0;
+      c[XV_REW_SUM] += reward;
+      if (reward < c[XV_REW_MIN]) c[XV_REW_MIN] = reward;
+      if (reward > c[XV_REW_MAX]) c[XV_REW_MAX] = reward;
+      if (t < c[XV_EP_FIRST]) c[XV_EP_FIRST] = t;
+      if (t > c[XV_EP_LAST]) c[XV_EP_LAST] = t;
+    }
+    a.mark[e] = n;
+  }
+}
+
 // sfl_curve.hip: queues one kernel on `stream` (a hipStream_t) -- the fold, or with `reset` the kernel that empties the
 // cells; 0, or -1 with the failing launch's name in *what and HIP's error code in *code
 int curve_launch(const CurveArgs& a, bool reset, void* stream, const char** what, int* code);
+// the same for the exploit record: k_curve_fold_exploit, or with `reset` the kernel that empties its cells
+int curve_xlaunch(const CurveXArgs& a, bool reset, void* stream, const char** what, int* code);
 
 }  // namespace sfl

@@ -91,6 +91,15 @@ struct Handle {
     CurveArgs a{};
     float last_ms = 0.f;
     double total_ms = 0.0;
+    // the exploit record (sfl_curve_exploit): x_on from the first call with f >= 1 to the curve's end;
+    // x_freq is what sfl_step launches with (0 after sfl_curve_exploit(h, 0)), xa.f what the rounds are counted with;
+    // x_limit [E]: the buffer xa.limit points at while x_freq == 0; the exploit fold's share of last_ms / total_ms
+    bool x_on = false;
+    int32_t x_freq = 0;
+    CurveXArgs xa{};
+    int32_t* x_limit = nullptr;
+    float x_last_ms = 0.f;
+    double x_total_ms = 0.0;
   } cv;
 
   template <class T>
@@ -613,6 +622,8 @@ int set_hparam_groups(Handle<B>* h, int32_t n_groups, const sfl_hparam_group* gr
 
 template <class B>
 int part_host_access(Handle<B>* h, bool write);
+template <class B>
+int curve_exploit_sync(Handle<B>* h);
 
 // rng_states: [E][5] (state hi, state lo, inc hi, inc lo, has<<32|buf) — numpy's
 // default_rng(seed).bit_generator.state, computed on the host.
@@ -636,6 +647,10 @@ int learn_begin(Handle<B>* h, const uint64_t* rng_states) {
   if (h->cv.on) {  // the curve starts over with the episode indices: marks at 0, cells empty
     h->be.memset(h->cv.a.mark, 0, E * 4);
     if (h->be.curve(h->cv.a, true)) return fail(std::string("sfl_learn_begin: ") + h->be.error());
+    if (h->cv.x_on) {  // and so does the exploit record: no round completed, none in flight
+      if (h->be.curve_exploit(h->cv.xa, true)) return fail(std::string("sfl_learn_begin: ") + h->be.error());
+      if (int rc = curve_exploit_sync(h)) return rc;
+    }
   }
   return h->be.sync() ? fail(h->be.error()) : 0;
 }
@@ -658,7 +673,8 @@ int mark_exploit_done(Handle<B>* h) {
   h->be.d2h(fl.data(), h->st.eflags, E * 4);
   for (auto& f : fl) f |= F_EXPLOIT_DONE;
   h->be.h2d(h->st.eflags, fl.data(), E * 4);
-  return h->be.sync() ? fail(h->be.error()) : 0;
+  if (h->be.sync()) return fail(h->be.error());
+  return curve_exploit_sync(h);  // (no row was written for the rounds the flag now claims: they are not folded)
 }
 
 // Q-init patch rows (distr_q.py:81-181): the same rows for every env
@@ -788,6 +804,12 @@ int run(Handle<B>* h, const SflCtl& c_in, sfl_run_args* args) {
     c.st_ticks = const_cast<int32_t*>(a.st_ticks);
     c.st_delays = const_cast<int32_t*>(a.st_delays);
   }
+  // ... and with an exploit record the greedy rounds' rows too (c.exploit_freq: sfl_step's, the record's frequency)
+  const bool xfold = curve && h->cv.x_on;
+  if (xfold) {
+    c.sx_cum = const_cast<double*>(h->cv.xa.sx_cum);
+    c.sx_arrived = const_cast<int32_t*>(h->cv.xa.sx_arrived);
+  }
   c.launch_dec = h->d_launch_dec;
   c.launch_ticks = h->d_launch_ticks;
   c.launch_bytes = h->d_launch_bytes;
@@ -811,6 +833,7 @@ int run(Handle<B>* h, const SflCtl& c_in, sfl_run_args* args) {
   int rc = h->be.run(h->map, h->st, c, h->variant, &ms);
   h->last_kernel_ms = ms;
   if (!rc && curve) rc = h->be.curve(h->cv.a, false);  // (timed on its own: elapsed_ms after the sync below)
+  if (!rc && xfold) rc = h->be.curve_exploit(h->cv.xa, false);  // (likewise: elapsed_exploit_ms)
   if (!rc && args && cap > 0) {
     if (args->cum_reward) h->be.d2h(args->cum_reward, c.st_cum, (size_t)cap * E * 8);
     if (args->arrived) h->be.d2h(args->arrived, c.st_arrived, (size_t)cap * E * 4);
@@ -830,7 +853,10 @@ int run(Handle<B>* h, const SflCtl& c_in, sfl_run_args* args) {
   if (rc) return fail(std::string("sfl_run: ") + h->be.error());
   if (curve) {
     h->cv.last_ms = h->be.elapsed_ms();
+    h->cv.x_last_ms = xfold ? h->be.elapsed_exploit_ms() : 0.f;
+    h->cv.last_ms += h->cv.x_last_ms;
     h->cv.total_ms += h->cv.last_ms;
+    h->cv.x_total_ms += h->cv.x_last_ms;
   }
   return check_errors(h);
 }
@@ -1504,6 +1530,10 @@ int curve_end(Handle<B>* h) {
   if (!h->cv.on) return fail("sfl_curve_end: the handle has no curve (sfl_curve_begin)");
   if (h->be.sync()) return fail(h->be.error());
   const CurveArgs& a = h->cv.a;
+  const CurveXArgs& x = h->cv.xa;  // (all null without an exploit record)
+  for (const void* p : {(const void*)x.mark, (const void*)x.sx_cum, (const void*)x.sx_arrived, (const void*)x.cells,
+                        (const void*)h->cv.x_limit})
+    if (p) h->dfree((void*)p);
   for (const void* p : {(const void*)a.mark, (const void*)a.series, (const void*)a.st_cum, (const void*)a.st_arrived,
                         (const void*)a.st_mf, (const void*)a.st_dec, (const void*)a.st_ticks, (const void*)a.st_delays,
                         (const void*)a.cells})
@@ -1611,6 +1641,115 @@ template <class B>
 int curve_skip_to_now(Handle<B>* h) {
   if (!h->cv.on) return 0;
   h->be.d2d(h->cv.a.mark, h->st.ep_t, (size_t)h->E * 4);
+  if (h->be.sync()) return fail(h->be.error());
+  return curve_exploit_sync(h);
+}
+
+// ---- the exploit record (include/sfl.h sfl_curve_exploit; sfl_curve.h) ----
+static_assert(CVX_DONE == F_EXPLOIT_DONE, "sfl_curve.h reads F_EXPLOIT_DONE from the flags word");
+
+// The marks set to the rounds every env has completed by now, so that the next fold takes up from here (a new record,
+// after sfl_learn_begin, sfl_learn and sfl_mark_exploit_done).  After sfl_curve_exploit(h, 0) also the limits: an env
+// completes the round it is in (its greedy flag holds until its next reset) and no other.
+template <class B>
+int curve_exploit_sync(Handle<B>* h) {
+  if (!h->cv.x_on) return 0;
+  const size_t E = h->E;
+  CurveXArgs& x = h->cv.xa;
+  std::vector<int32_t> ep(E), ph(E), mark(E), limit;
+  std::vector<uint32_t> fl(E);
+  h->be.d2h(ep.data(), h->st.ep_t, E * 4);
+  h->be.d2h(ph.data(), h->st.phase, E * 4);
+  h->be.d2h(fl.data(), h->st.eflags, E * 4);
+  if (h->be.sync()) return fail(h->be.error());
+  for (size_t e = 0; e < E; ++e) mark[e] = curve_rounds_done(ep[e], fl[e], x.f);
+  h->be.h2d(x.mark, mark.data(), E * 4);
+  x.limit = nullptr;
+  if (h->cv.x_freq == 0) {
+    limit.resize(E);
+    for (size_t e = 0; e < E; ++e) {
+      const bool in_flight = (fl[e] & F_GREEDY) && !(fl[e] & F_EXPLOIT_DONE) && ph[e] != PH_RESET;
+      limit[e] = mark[e] + (in_flight ? 1 : 0);
+    }
+    h->be.h2d(h->cv.x_limit, limit.data(), E * 4);
+    x.limit = h->cv.x_limit;
+  }
+  return h->be.sync() ? fail(h->be.error()) : 0;  // (the host sources of the uploads live until here)
+}
+
+template <class B>
+int curve_exploit(Handle<B>* h, int32_t f) {
+  if (f < 0) return fail("sfl_curve_exploit: exploit_freq must not be negative");
+  if (!h->cv.on) return fail("sfl_curve_exploit: the handle has no curve (sfl_curve_begin)");
+  if (f == 0) {  // no new round starts; the record stays
+    if (!h->cv.x_on) return 0;
+    h->cv.x_freq = 0;
+    return curve_exploit_sync(h);
+  }
+  const CurveArgs& a = h->cv.a;
+  const size_t E = h->E, R = (size_t)a.ring_cap;
+  if (!h->cv.x_on) {
+    const uint64_t ring_bytes = (uint64_t)a.ring_cap * E * (24 + 4 * (uint64_t)a.T + 12);
+    if (ring_bytes > SFL_CURVE_MAX_RING_BYTES)
+      return fail("sfl_curve_exploit: with the rounds' rows the ring of " + std::to_string(a.ring_cap) + " rows takes " +
+                  std::to_string(ring_bytes) + " bytes, above " + std::to_string(SFL_CURVE_MAX_RING_BYTES) +
+                  " (SFL_CURVE_MAX_RING_BYTES)");
+    CurveXArgs x{};
+    x.E = a.E;
+    x.n_series = a.n_series;
+    x.T = a.T;
+    x.n_bins = a.n_bins;
+    x.bin_episodes = a.bin_episodes;
+    x.ring_cap = a.ring_cap;
+    x.ep_t = h->st.ep_t;
+    x.eflags = h->st.eflags;
+    x.series = a.series;
+    x.mark = h->template dalloc<int32_t>(E);
+    x.sx_cum = h->template dalloc<double>(R * E);
+    x.sx_arrived = h->template dalloc<int32_t>(R * E);
+    x.cells = h->template dalloc<int64_t>((size_t)a.n_bins * a.n_series * XV_WORDS);
+    h->cv.x_limit = h->template dalloc<int32_t>(E);
+    h->cv.xa = x;
+    if (!x.mark || !x.sx_cum || !x.sx_arrived || !x.cells || !h->cv.x_limit) {
+      for (const void* p : {(const void*)x.mark, (const void*)x.sx_cum, (const void*)x.sx_arrived, (const void*)x.cells,
+                            (const void*)h->cv.x_limit})
+        if (p) h->dfree((void*)p);
+      h->cv.xa = CurveXArgs{};
+      h->cv.x_limit = nullptr;
+      return fail("sfl_curve_exploit: device allocation failed (ring or cells)");
+    }
+    h->be.memset((void*)x.sx_cum, 0, R * E * 8);
+    h->be.memset((void*)x.sx_arrived, 0, R * E * 4);
+    h->cv.x_on = true;
+  }
+  CurveXArgs& x = h->cv.xa;
+  int32_t g = a.ring_cap, r = f;  // gcd(ring_cap, f)
+  while (r) {
+    const int32_t t = g % r;
+    g = r;
+    r = t;
+  }
+  x.f = f;
+  x.period = a.ring_cap / g;
+  h->cv.x_freq = f;
+  if (h->be.curve_exploit(x, true)) return fail(std::string("sfl_curve_exploit: ") + h->be.error());
+  return curve_exploit_sync(h);
+}
+
+template <class B>
+int curve_read_exploit(Handle<B>* h, sfl_curve_xcell* out) {
+  if (!h->cv.x_on) return fail("sfl_curve_read_exploit: the handle has no exploit record (sfl_curve_exploit)");
+  if (!out) return fail("sfl_curve_read_exploit: null argument");
+  const CurveXArgs& x = h->cv.xa;
+  h->be.d2h(out, x.cells, (size_t)x.n_bins * x.n_series * sizeof(sfl_curve_xcell));
+  return h->be.sync() ? fail(h->be.error()) : 0;
+}
+
+template <class B>
+int curve_rounds(Handle<B>* h, int32_t* out) {
+  if (!h->cv.x_on) return fail("sfl_curve_rounds: the handle has no exploit record (sfl_curve_exploit)");
+  if (!out) return fail("sfl_curve_rounds: null argument");
+  h->be.d2h(out, h->cv.xa.mark, (size_t)h->E * 4);
   return h->be.sync() ? fail(h->be.error()) : 0;
 }
 

@@ -93,6 +93,13 @@ struct HostBackend {
     else sfl::curve_fold_host(a);
     return 0;
   }
+  // sfl_curve_exploit: the exploit record's fold (or its cells' reset) as plain loops (sfl_curve.h)
+  int curve_exploit(const sfl::CurveXArgs& a, bool reset) {
+    if (reset) sfl::curve_xreset_host(a);
+    else sfl::curve_xfold_host(a);
+    return 0;
+  }
+  float elapsed_exploit_ms() { return 0.f; }
   int sync() { return 0; }
   uint64_t n_wait = 0;  // (nothing to wait for: the host build runs on the caller's thread)
   const uint32_t* seedseq_table() { return nullptr; }  // the host build draws every sub-generator

@@ -289,16 +289,29 @@ class Batch:
             warnings.warn(f"step({d}) may end up to {d + 1} episodes per env, more than the curve's ring of {ring} rows: "
                           f"the overwritten ones are counted in `lost` (curve_begin(ring={d + 1}) keeps them all)",
                           RuntimeWarning, stacklevel=2)
+        f = getattr(self, "_curve_xfreq", None)
+        if ring is not None and f and not self._curve_xwarned:
+            import math
+            import warnings
+            p = ring // math.gcd(ring, f)
+            if p < d + 1:
+                self._curve_xwarned = True
+                warnings.warn(f"step({d}) may end up to {d + 1} exploit rounds per env, but rounds {p} apart share a row "
+                              f"of the curve's ring ({ring} rows, exploit_freq {f}): the overwritten ones are counted in "
+                              f"`exploit_lost` (a ring of {d + 1} or more rows that is coprime to {f} keeps them all)",
+                              RuntimeWarning, stacklevel=2)
         self.lib.check(self.lib.dll.sfl_step(self.h, d, C.byref(n), C.byref(ms)), "sfl_step")
         return int(n.value), float(ms.value)
 
     # ---- step-mode learning curves (sfl_curve_*): the episodes step() ends, reduced on the device ----
-    def curve_ring_max(self) -> int:
-        """The most ring rows sfl_curve_begin accepts for this batch (SFL_CURVE_MAX_RING_BYTES)."""
-        return max(1, _lib.CURVE_MAX_RING_BYTES // (self.E * (24 + 4 * self.cm.T)))
+    def curve_ring_max(self, exploit: bool = False) -> int:
+        """The most ring rows sfl_curve_begin accepts for this batch (SFL_CURVE_MAX_RING_BYTES); ``exploit``: for a
+        curve with an exploit record (sfl_curve_exploit: 12 more bytes per row and env)."""
+        return max(1, _lib.CURVE_MAX_RING_BYTES // (self.E * (24 + 4 * self.cm.T + (12 if exploit else 0))))
 
     def curve_begin(self, bin_episodes: int, n_bins: int, series: Optional[Sequence[int]] = None,
-                    n_series: Optional[int] = None, ring: Optional[int] = None) -> int:
+                    n_series: Optional[int] = None, ring: Optional[int] = None,
+                    exploit_freq: Optional[int] = None) -> int:
         """Start recording learning curves in step mode (include/sfl.h sfl_curve_begin): from now on every ``step``
         folds the episodes it ended into a table of ``n_bins`` x ``n_series`` cells -- episode i of an env in bin
         min(i // bin_episodes, n_bins - 1), env e in series ``series[e]``.  ``series=None``: each env's hyperparameter
@@ -306,7 +319,14 @@ class Batch:
         defaults to the highest id + 1.  ``ring``: statistics rows kept per env between folds; a ``step(D)`` ends at
         most D + 1 episodes per env, so ``ring >= D + 1`` loses none.  ``ring=None`` picks min(D + 1, the most rows
         ``curve_ring_max()`` allows) with D the largest ``step`` this batch has run so far, or 64 if it has run none;
-        a later ``step(D)`` with D + 1 > ring warns once.  Returns the ring size.  Replaces a running curve."""
+        a later ``step(D)`` with D + 1 > ring warns once.  Returns the ring size.  Replaces a running curve.
+
+        ``exploit_freq=f`` (f >= 1) also starts the curve's exploit record (``curve_exploit``): ``step`` then runs the
+        reference's greedy round before every learning episode t with (t + 1) % f == 0 (distr_q.py:278-281) and
+        ``curve()`` reports the rounds as ``exploit_*``.  Rounds ring / gcd(ring, f) apart share a ring row, so
+        ``ring=None`` then picks the smallest ring at or above the value described above that is coprime to f (the
+        largest one that fits if ``curve_ring_max(exploit=True)`` is below that), and with ``ring >= D + 1`` a
+        ``step(D)`` loses no round; with an explicit ring ``step(D)`` warns once if ring / gcd(ring, f) < D + 1."""
         if series is None:
             ptr = None
             n = len(self.hparam_groups) or 1
@@ -320,20 +340,50 @@ class Batch:
             ptr = _ptr(arr, C.c_uint32)
             n = max(ids) + 1
         n = n if n_series is None else int(n_series)
+        f = int(exploit_freq or 0)
         if ring is None:
-            ring = min((getattr(self, "_largest_step", 0) or 64) + 1, self.curve_ring_max())
+            import math
+            most = self.curve_ring_max(exploit=f > 0)
+            ring = min((getattr(self, "_largest_step", 0) or 64) + 1, most)
+            if f > 0:
+                up = next(r for r in range(ring, ring + f + 1) if math.gcd(r, f) == 1)  # (k f + 1 is coprime to f)
+                ring = up if up <= most else next(r for r in range(most, 0, -1) if math.gcd(r, f) == 1)
         self.lib.check(self.lib.dll.sfl_curve_begin(self.h, int(bin_episodes), int(n_bins), n, ptr, int(ring)),
                        "sfl_curve_begin")
         self._curve_shape = (int(n_bins), n)
         self._curve_ring = int(ring)
-        self._curve_warned = False
+        self._curve_warned = self._curve_xwarned = False
+        self._curve_xfreq = None
+        if f > 0:
+            self.curve_exploit(f)
         return int(ring)
+
+    def curve_exploit(self, exploit_freq: int) -> None:
+        """Start, change or stop the exploit record of the running curve (include/sfl.h sfl_curve_exploit).  f >= 1:
+        every later ``step`` runs a greedy round before each learning episode t with (t + 1) % f == 0, as
+        ``learn(N, exploit_freq=f)`` does, and folds the rounds it ends into ``curve()``'s ``exploit_*`` cells; the
+        call empties those cells and counts rounds from where each env stands.  f == 0: no new round starts, a round in
+        flight is finished and folded, the cells stay readable.  Not the reference's: with f == 1 an env standing at
+        episode 0 runs its first round on the initialised Q-table (``learn`` runs it before the Q-init rows are
+        applied); and greedy decisions count towards ``step``'s decisions per env and ``counters()["decisions"]``,
+        as they do in ``learn``."""
+        if getattr(self, "_curve_shape", None) is None:
+            raise _lib.SflError("curve_exploit: no curve on this batch (curve_begin)")
+        f = int(exploit_freq)
+        self.lib.check(self.lib.dll.sfl_curve_exploit(self.h, f), "sfl_curve_exploit")
+        if f > 0 or self._curve_xfreq is not None:
+            self._curve_xfreq = f
+            self._curve_xwarned = False
 
     def curve(self) -> Dict[str, np.ndarray]:
         """The curve so far: one int64 array [n_bins][n_series] per field of sfl_curve_cell (``_lib.CURVE_FIELDS``);
         ``episodes`` [E], each env's learning episodes accounted for (folded or lost); and the float means
         ``arrived_mean``, ``reward_mean``, ``decisions_per_episode``, ``ticks_per_decision``, ``truncated_frac`` and
-        ``all_arrived_frac`` over the folded episodes of each cell, NaN where ``count == 0``."""
+        ``all_arrived_frac`` over the folded episodes of each cell, NaN where ``count == 0``.  While the curve has an
+        exploit record (``curve_begin(exploit_freq=)`` / ``curve_exploit``) also ``exploit_<field>`` for the fields of
+        sfl_curve_xcell (``_lib.CURVE_XFIELDS``), ``exploit_rounds`` [E], each env's greedy rounds accounted for, and
+        ``exploit_arrived_mean``, ``exploit_reward_mean``, ``exploit_all_arrived_frac`` over the folded rounds of each
+        cell, NaN where ``exploit_count == 0``."""
         if getattr(self, "_curve_shape", None) is None:
             raise _lib.SflError("curve: no curve on this batch (curve_begin)")
         nb, ns = self._curve_shape
@@ -353,10 +403,31 @@ class Batch:
             out["all_arrived_frac"] = per_ep("all_arrived")
             out["ticks_per_decision"] = np.where((cnt > 0) & (out["decisions_sum"] > 0),
                                                  out["ticks_sum"] / out["decisions_sum"].astype(np.float64), np.nan)
+        if getattr(self, "_curve_xfreq", None) is not None:
+            xc = np.zeros((nb, ns, len(_lib.CURVE_XFIELDS)), np.int64)
+            self.lib.check(self.lib.dll.sfl_curve_read_exploit(self.h, _ptr(xc, C.c_int64)), "sfl_curve_read_exploit")
+            rounds = np.zeros(self.E, np.int32)
+            self.lib.check(self.lib.dll.sfl_curve_rounds(self.h, _ptr(rounds, C.c_int32)), "sfl_curve_rounds")
+            for i, k in enumerate(_lib.CURVE_XFIELDS):
+                out["exploit_" + k] = np.ascontiguousarray(xc[:, :, i])
+            out["exploit_rounds"] = rounds
+            xn = out["exploit_count"].astype(np.float64)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                for k, num in (("arrived_mean", "arrived_sum"), ("reward_mean", "reward_sum"),
+                               ("all_arrived_frac", "all_arrived")):
+                    out["exploit_" + k] = np.where(xn > 0, out["exploit_" + num] / xn, np.nan)
         return out
 
+    def curve_exploit_fold_ms(self) -> Tuple[float, float]:
+        """Device ms of the exploit record's last fold and of all its folds (part of ``curve_fold_ms``'s figures)."""
+        last, total = C.c_double(0.0), C.c_double(0.0)
+        self.lib.check(self.lib.dll.sfl_curve_exploit_fold_ms(self.h, C.byref(last), C.byref(total)),
+                       "sfl_curve_exploit_fold_ms")
+        return float(last.value), float(total.value)
+
     def curve_fold_ms(self) -> Tuple[float, float]:
-        """Device ms of the last fold and of all folds since ``curve_begin`` (never part of ``step``'s kernel ms)."""
+        """Device ms of the last fold and of all folds since ``curve_begin`` (never part of ``step``'s kernel ms); with
+        an exploit record both of its folds."""
         last, total = C.c_double(0.0), C.c_double(0.0)
         self.lib.check(self.lib.dll.sfl_curve_fold_ms(self.h, C.byref(last), C.byref(total)), "sfl_curve_fold_ms")
         return float(last.value), float(total.value)
@@ -364,7 +435,7 @@ class Batch:
     def curve_end(self) -> None:
         """Stop recording and free the ring and the table: ``step`` runs as on a batch that never had a curve."""
         self.lib.check(self.lib.dll.sfl_curve_end(self.h), "sfl_curve_end")
-        self._curve_shape = self._curve_ring = None
+        self._curve_shape = self._curve_ring = self._curve_xfreq = None
 
     PHASES = ("tick", "observe", "egreedy", "apply", "post", "reset", "other")
 
