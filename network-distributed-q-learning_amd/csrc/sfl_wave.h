@@ -92,18 +92,6 @@ __device__ __forceinline__ int32_t d16_lo(uint32_t w) {
   return v == -32768 ? (int32_t)0x80000000 : (v == 32767 ? DIST_INF : v);
 }
 __device__ __forceinline__ int32_t d16_hi(uint32_t w) { return d16_lo(w >> 16); }
-// epsilon staged with the batch (round 6): the grouped shapes (G < 64, <= 64 switches) stage, with each queued
-// train's record, eps_tab[n] of its decision switch as the switch's interaction count n stands at staging (record
-// double 3); the decision compares against it instead of loading eps_tab[n] behind the count (one dependent vector
-// load off the decision's chain).  A switch decided on since the staging has a stale value (its count moved): the
-// env's LDS word lrng[5] marks those switches, and their decisions load eps_tab[n] as before.  Measured and NOT the
-// default (profiles/r06e_eps_staging_ab.txt, same box, parity ok): c3 1,590-1,593 M vs 1,611-1,612 M, c2 at 4,096
-// envs 335.5 M vs 345.6 M -- the staged value's live range and the lrng[5] read-modify-write cost the variant-7 kernel
-// 12 more spill instructions (40 -> 52, scripts/spills.py), some of them in the decision and staging paths, and the
-// staging adds a counter read and a load to every staged record.  1: on (A/B builds)
-#ifndef SFL_EPS_PF
-#define SFL_EPS_PF 0
-#endif
 #ifndef SFL_WAVE_BLOCK
 #define SFL_WAVE_BLOCK 256  // threads per k_wave block (envs per block x 64)
 #endif
@@ -336,11 +324,6 @@ struct WEnv {
   static constexpr int RING_N = G < 64 ? SFL_PF_RING : SFL_PF_RING64;
   static constexpr bool RING = !PART && !EXT && TPL > 1 && RING_N > 0 && RING_N < TWc;
   static constexpr int PF_SLOTS = (PART || EXT) ? 1 : (RING ? RING_N : TWc);
-  // (SFL_EPS_PF) the record's doubles: + the staged epsilon
-  // (HPG: the staging reads the map's own table, so grouped handles decide on the loaded value)
-  static constexpr bool EPS_PF = SFL_EPS_PF && !PART && !EXT && G < 64 && G * SPL <= 64 && !HPG;
-  static constexpr int PFD = EPS_PF ? PF_D + 1 : PF_D;
-  static constexpr int PFW = 2 * PFD + PF_WI;
   __device__ __forceinline__ static int pfx(int h) { return (PART || EXT) ? 0 : h; }
   // RING: record i is staged by lane i % G (register slot i / G) in one pass per G records -- the lanes
   // stage the batch's queued trains in queue order, so a batch of up to G decisions is one set of
@@ -377,7 +360,7 @@ struct WEnv {
   uint32_t* lcnt;  // [64*SPL]
   // batch prefetch (see prefetch()): per queued train (lane), the staged Q row, the pending
   // update's Q cell value and the slot word in LDS, and the staged offsets in VGPRs
-  double* lpf;       // [TW][PFD]: pending cell value | slot word (as bits) | row max (| staged epsilon)
+  double* lpf;       // [TW][PF_D]: pending cell value | slot word (as bits) | row max
   uint32_t* lpi;     // [TW][PF_WI]: int16 distances, argmaxes
   uint32_t pf_roff[PFS];  // offset of the staged row in the env's Q block (PF_NONE: none)
   uint32_t pf_qoff[PFS];  // offset of the staged pending cell (PF_NONE: none)
@@ -395,7 +378,7 @@ struct WEnv {
   Mask q_mask, arr_mask, fl_mask, mf_mask;
   // the epsilon-greedy stream (numpy PCG64 state, increment, buffered half) lives in LDS: it is
   // touched once per decision and would otherwise hold ten registers across the whole loop
-  uint64_t* lrng;  // [6]: state hi, lo, inc hi, lo, has << 32 | buf, (EPS_PF) switches decided since the staging
+  uint64_t* lrng;  // [6]: state hi, lo, inc hi, lo, has << 32 | buf, (MALF_LDS) the malfunctioning trains
   int64_t cum;     // cumulative reward: a sum of integer rewards, exact in f64 (converted on store)
   int32_t n_mf, ep_dec, ep_ticks;
   int32_t step_ctr;
@@ -438,12 +421,12 @@ struct WEnv {
     for (int k = 0; k < TPL; ++k) mine[k] = lane + G * k < m_.T;
 #pragma unroll
     for (int k = 0; k < PFS; ++k) pf_roff[k] = pf_qoff[k] = PF_NONE;
-    lpi = (uint32_t*)(lpf + PF_SLOTS * PFD);
-    lrng = (uint64_t*)(lds + G * (PPL + SPL) + PF_SLOTS * PFW);
+    lpi = (uint32_t*)(lpf + PF_SLOTS * PF_D);
+    lrng = (uint64_t*)(lds + G * (PPL + SPL) + PF_SLOTS * PF_WORDS);
     // PART: the timetable rows are read from the map (L2-resident): a launch runs one or two
     // decisions, so a per-launch LDS copy would cost more than it saves
     if constexpr (PART) ltt = m.tr_pack;
-    else ltt = ltt_shared ? ltt_shared : (const int32_t*)(lds + G * (PPL + SPL) + PF_SLOTS * PFW + 12);
+    else ltt = ltt_shared ? ltt_shared : (const int32_t*)(lds + G * (PPL + SPL) + PF_SLOTS * PF_WORDS + 12);
     pf_ok = false;
     if constexpr (PART) {  // the rows this rank owns, of this env (the env-local table is freed)
       const size_t ge = (size_t)P_->env_base + e_;
@@ -607,6 +590,18 @@ struct WEnv {
 #pragma unroll
     for (int k = 0; k < TPL; ++k) p[k] = mine_(k) && tb_state(bits[k]) == S_MALF;
     return mbal(p);
+  }
+  // Train states change only in tick(), reset() and load(): the grouped shapes whose mask is one or two words keep it
+  // in the env's LDS block between them (the spare words behind the epsilon-greedy stream, a group-uniform value
+  // written by every lane like sset) instead of two ballots with per-lane shifts in every decision and staging.
+  // G = 64 (a wave ballot in SGPRs) and the 128-train shapes compute it where it is used.
+  static constexpr bool MALF_LDS = G < 64 && sizeof(Mask) <= 8;
+  __device__ __forceinline__ void malf_keep(Mask v) {
+    if constexpr (MALF_LDS) *(Mask*)(lrng + 5) = v;
+  }
+  __device__ __forceinline__ Mask malf_kept() const {
+    if constexpr (MALF_LDS) return *(const Mask*)(lrng + 5);
+    else return malf_mask();
   }
 
   // ---- map records --------------------------------------------------------------------
@@ -1000,6 +995,7 @@ struct WEnv {
     ep_ticks = U(ld(s.ep_ticks, e));
     step_ctr = (int32_t)U(ld(s.step_ctr, e));
     n_dec = 0;
+    malf_keep(malf_mask());
   }
   // returns the env's error bits (OR over lanes); PART writes its scalars with store_eblk
   __device__ __forceinline__ uint32_t store(int32_t phase) {
@@ -1180,6 +1176,7 @@ struct WEnv {
     }
     flags &= ~(F_TERM | F_TRUNC | F_OWN_SCAN | F_INFLIGHT);
     q_mask = arr_mask = fl_mask = mf_mask = Mask{};
+    malf_keep(Mask{});
     // new (switch, train) epoch: slots from older episodes read as empty
     epoch = (epoch + 1u) & 0xFFu;
     if (epoch == 0) {
@@ -1370,7 +1367,7 @@ struct WEnv {
     }
     // pass 3: state machine + positions, deviation fix
     const bool over = t >= m.max_episode_steps;
-    bool done[TPL], isdone[TPL], newly[TPL], dep[TPL];
+    bool done[TPL], newdone[TPL], isdone[TPL], newly[TPL], dep[TPL];
 #pragma unroll
     for (int k = 0; k < TPL; ++k) {
       const int h = lid() + G * k;
@@ -1379,6 +1376,7 @@ struct WEnv {
       done[k] = false;
       isdone[k] = !mine_(k);
       newly[k] = false;
+      newdone[k] = false;
       dep[k] = false;
       if (mine_(k)) {
         const uint32_t b = bits[k];
@@ -1423,6 +1421,7 @@ struct WEnv {
         if (mf > 0) mf -= 1;
         if (np >= 0) saved = 0;
         done[k] = (st_ == S_DONE) || over;
+        newdone[k] = done[k] && !tb_done(b);
         isdone[k] = st_ == S_DONE;
         pos[k] = np;
         // switchfl: deviation fix
@@ -1438,17 +1437,11 @@ struct WEnv {
       }
     }
     arr_mask |= mbal(newly);
-    // delete the semaphores of done trains (switch_env.py:370-376): each lane its own records
-    const Mask DONE = mbal(done);
-    if (many(DONE)) {
-#pragma unroll
-      for (int k = 0; k < PPL; ++k) {
-        const uint32_t r = sem(k);
-        sem(k) = (r_present(r) & mbit(DONE, (int)r_owner(r))) ? 0u : r;
-      }
-    }
     // departure semaphores, in handle order (switch_env.py:379-384)
     Mask D = mbal(dep);
+    // the trains whose records this tick deletes (switch_env.py:370-376; the deletion itself is the pass below, behind
+    // the departure writes, which it therefore leaves alone: the reference deletes first and then writes them)
+    const Mask CLR = mbal(newdone) & ~D;
     while (many(D)) {
       const int j = mctz(D);
       mclear_low(D);
@@ -1465,15 +1458,34 @@ struct WEnv {
       mfp[k] = mine_(k) && tb_mf(bits[k]) > 0;
     }
     const Mask SM = mbal(smp);
-    if (many(SM)) {
+    // One pass over the lane's own records: delete those of the trains that became done in this tick, retime those of
+    // stopped and malfunctioning trains.  A train that was done before this tick has no record left -- its arrival
+    // tick deleted them, and a train off the map is never queued, never departs and never malfunctions on the map,
+    // so nothing writes one for it again -- which is why the deletion asks for the new done flag against the one the
+    // train's bits carried into the tick (newdone), not for the done trains of every tick.  The lane's base address
+    // is taken once, here (not held across the tick), and the words are at the compile-time offsets k * G.
+    if (many(CLR | SM)) {
+      uint32_t* const w = lsem + lid();
 #pragma unroll
       for (int k = 0; k < PPL; ++k) {
-        const uint32_t r = sem(k);
-        const bool ext = r_present(r) & mbit(SM, (int)r_owner(r));
-        sem(k) = ext ? r_retime(r, t) : r;
+        const uint32_t r = w[k * G];
+        if constexpr (sizeof(Mask) == 4) {
+          // up to 32 trains (a record's owner is a train, so below 32): the two selections as bit masks, no compares
+          const uint32_t o = r_owner(r) & 31u;
+          const uint32_t p = (uint32_t)((int32_t)r >> 31);  // present: all ones
+          // (v_bfe_i32: bit o of the mask, sign-extended)
+          const uint32_t cm = (uint32_t)__builtin_amdgcn_sbfe((int)(uint32_t)CLR, o, 1u);
+          const uint32_t tm = (uint32_t)__builtin_amdgcn_sbfe((int)(uint32_t)SM, o, 1u) & p & R_T0_MASK;
+          w[k * G] = ((r & ~tm) | ((uint32_t)t & tm)) & ~(cm & p);
+        } else {
+          const int o = (int)r_owner(r);
+          const uint32_t x = mbit(CLR, o) ? 0u : (mbit(SM, o) ? r_retime(r, t) : r);
+          w[k * G] = r_present(r) ? x : r;
+        }
       }
     }
     Mask MA = mbal(map_);
+    malf_keep(MA);  // the malfunctioning trains until the next tick (malf_kept)
     while (many(MA)) {
       const int j = mctz(MA);
       mclear_low(MA);
@@ -1534,11 +1546,10 @@ struct WEnv {
   // stale: a decision writes only its own train's slots and a train decides once per batch.
   __device__ __forceinline__ void prefetch(bool greedy) {
     PrioGuard<PART ? 0 : SFL_SETPRIO_PF> prio;
-    const Mask malf = malf_mask();
+    const Mask malf = malf_kept();
 #pragma unroll
     for (int k = 0; k < PFS; ++k) pf_roff[k] = pf_qoff[k] = PF_NONE;
     pf_n = 0;
-    if constexpr (EPS_PF) lrng[5] = 0ull;  // (uniform value from every lane) the staged epsilons are current
     if constexpr (PF_BY_RANK) {
       // lane i stages the i-th queued train (record i = the i-th decision of the batch); trains beyond the
       // records wait for the next staging
@@ -1603,7 +1614,7 @@ struct WEnv {
     const int slot = pin & 3;
     const int dir0 = (int)tb_dir(bits_k);
     const int pos0 = pos_k >= 0 ? pos_k : 0;
-    double* pfl = lpf + PFD * rec;
+    double* pfl = lpf + PF_D * rec;
     uint32_t* pfi = lpi + PF_WI * rec;
     // level 1: slot word, switch record, timetable row, the row block's port record, first moves
     const uint64_t slw = ld(sbase(), slot_ix(sw, hk));
@@ -1696,14 +1707,6 @@ struct WEnv {
 #pragma unroll
       for (int c = 0; c < 4; ++c) rv[c] = ld(rp, (size_t)((uint32_t)c < w ? c : 0));
       qv = ld(qbase(), (size_t)(hp ? qoff : 0u));
-    }
-    // (EPS_PF) eps0 * decay**n of the decision switch at its present count (distr_q.py:59-68), with the Q loads (a
-    // short live range); beyond the table the decision computes it
-    if constexpr (EPS_PF) {
-      const uint32_t n_s = cget_var(sw);
-      double eps_v = 0.0;
-      if (!greedy && n_s < (uint32_t)m.ntab) eps_v = ld(m.eps_tab, (size_t)n_s);
-      pfl[3] = eps_v;
     }
     // the greedy choice on the staged row (distr_q.py:449-490, as in decide): valid whenever the
     // row is (a decision uses it only if its observation is the staged one)
@@ -1816,7 +1819,7 @@ struct WEnv {
     const vec_t<int32_t, 8> tr = tr_row(h);
     const int rec = RING ? pf_n : pfx(h);
     if constexpr (RING) pf_n += 1;
-    const double* pfh = lpf + PFD * rec;
+    const double* pfh = lpf + PF_D * rec;
     const uint32_t* pfw = lpi + PF_WI * rec;
     // the decision's LDS reads that do not depend on its observation, issued together: the staged
     // slot word (never stale: a decision writes only its own train's slots), row column, pending
@@ -1830,6 +1833,7 @@ struct WEnv {
 #pragma unroll
     for (int i = 0; i < 5; ++i) rng_w[i] = lrng[i];
     const uint32_t n_sw = cget(sw);
+    const Mask malf = malf_kept();
     const int pidx = PF_BY_RANK ? rec : h;  // the staged offsets' record
     const uint32_t pf_roff_h = rec_of(pf_roff, pidx), pf_qoff_h = rec_of(pf_qoff, pidx);
     const int np = swr.np();
@@ -1850,7 +1854,6 @@ struct WEnv {
     const uint32_t nbl = ((lid() & 2) ? nbw[1] : nbw[0]) >> ((lid() & 1) * 16);
     const bool pvalid = lid() < np;
     const int nbj = pvalid ? (int)(nbl & 0xFFFFu) : pj;
-    const Mask malf = malf_mask();
     const uint32_t rn = lsem[nbj], ro = lsem[pj];
     const uint32_t blk = rec_blocks(rn, (uint32_t)h, malf, 0u) | rec_blocks(ro, (uint32_t)h, malf, 1u);
     const uint32_t free_bits = (uint32_t)BAL(pvalid && blk == 0u) & 15u;
@@ -1937,15 +1940,7 @@ struct WEnv {
       if (xp::kEpsConst) {
         explore = ud < eps0_();
       } else {
-        // (EPS_PF) the staged value, unless the switch was decided on since the staging (its count moved)
-        bool staged = false;
-        double eps_st = 0.0;
-        if constexpr (EPS_PF) {
-          staged = !((lrng[5] >> sw) & 1ull) && n < (uint32_t)m.ntab;
-          eps_st = pfh[3];
-        }
-        explore = ud < (staged ? eps_st
-                               : (n < (uint32_t)m.ntab ? LDC(eps_row(), (size_t)n) : eps0_() * pow_ool(eps_decay_(), (double)n)));
+        explore = ud < (n < (uint32_t)m.ntab ? LDC(eps_row(), (size_t)n) : eps0_() * pow_ool(eps_decay_(), (double)n));
       }
       if (explore && !observe_only) {
         const uint32_t sub_seed = pcg_bounded(rng, 2147483646u);
@@ -1980,7 +1975,6 @@ struct WEnv {
         lrng[4] = ((uint64_t)rng.has << 32) | rng.buf;
       }
     }
-    if constexpr (EPS_PF) lrng[5] |= 1ull << sw;  // (uniform) this switch's count moves in post
     if constexpr (PART) {
       if (observe_only) {
         emit_req(sw, slot, state, amask, explore);
@@ -2573,7 +2567,7 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
   // semaphores, counters, prefetch records, rng, timetable (PART: one record, timetable from the map)
   // (PART: the launch's initial records / counters in place of the timetable copy)
   constexpr int LDS_WORDS =
-      64 * (PPL + SPL) + V::PF_SLOTS * V::PFW + 12 + (PART ? 64 * PPL + 2 * SPL + 6 * 64 * V::TPL : TW * 8);
+      64 * (PPL + SPL) + V::PF_SLOTS * PF_WORDS + 12 + (PART ? 64 * PPL + 2 * SPL + 6 * 64 * V::TPL : TW * 8);
   const int lane = (int)__lane_id();
   const uint32_t e = uni((uint32_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
   if (e >= s.E) return;
@@ -2581,7 +2575,7 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
   __shared__ uint32_t lds[WPB * LDS_WORDS];
   V v(m, s, e, lane, lds + (threadIdx.x >> 6) * LDS_WORDS, P);
   if constexpr (PART) {
-    v.lsem0 = lds + (threadIdx.x >> 6) * LDS_WORDS + 64 * (PPL + SPL) + V::PF_SLOTS * V::PFW + 12;
+    v.lsem0 = lds + (threadIdx.x >> 6) * LDS_WORDS + 64 * (PPL + SPL) + V::PF_SLOTS * PF_WORDS + 12;
     v.ldirty = v.lsem0 + 64 * PPL;
     v.ltr0 = v.ldirty + 2 * SPL;
   }
@@ -2723,13 +2717,15 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
   // per env: semaphores, counters, prefetch records, rng; per block: the timetable rows and the
   // per-switch / per-port map records (the groups of a wave read different switches' records: LDS
   // reads instead of vector loads)
-  constexpr int LDS_WORDS = (G * (PPL + SPL) + V::PF_SLOTS * V::PFW + 12 + 3) / 4 * 4;
+  constexpr int LDS_WORDS = (G * (PPL + SPL) + V::PF_SLOTS * PF_WORDS + 12 + 3) / 4 * 4;
   constexpr int EPB = SFL_GROUP_BLOCK / G;  // envs per block (sfl.hip launches)
   constexpr int SWX = G * SPL, NPX = G * PPL;  // switches / ports the shape holds
   constexpr int O_TT = EPB * LDS_WORDS, O_SW = O_TT + TW * 8, O_PP = O_SW + SWX * V::SW_LDS, O_PT = O_PP + NPX * 4;
   // LM: the move table and the distance map (int16 pairs) after the map records, within 64,512 bytes
   // (sfl_engine.h kLmBytes: two such blocks fill the CU's LDS)
   constexpr int O_LM = O_PT + NPX * 4, LM_WORDS = LM ? 16128 : 0;
+  // (LM shapes are launched two blocks to a CU: both blocks' LDS must fit its 160 KB)
+  static_assert(!LM || 2 * (O_LM + LM_WORDS) * 4 <= 163840, "LM: two blocks' LDS exceed a CU's 160 KB");
   __shared__ __attribute__((aligned(16))) uint32_t lds[O_LM + LM_WORDS];
   for (int i = (int)threadIdx.x; i < m.S * V::SW_LDS; i += (int)blockDim.x)
     lds[O_SW + i] = m.sw_pack[(i / V::SW_LDS) * 16 + i % V::SW_LDS];
