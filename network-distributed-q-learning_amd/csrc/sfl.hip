@@ -97,12 +97,18 @@ __global__ void __launch_bounds__(256) k_part_local(const sfl::SflMap* __restric
   if (e < s->E) sfl::env_run_part<NW>(*m, *s, *c, *P, e);
 }
 // after the local step: pack each env's staged request and update records into the destination
-// segments, each env's records for one destination as a contiguous group (sfl_part.h env_groups: its
-// updates in emission order, then its request) -- a block reserves its range per destination with one
-// global atomic, the envs their groups in it with LDS atomics -- and add the launch totals of the envs
-// that ran into P->sums.  A segment holds k_msg records this round: an env with a group that reaches past
-// that place is deferred whole (F_DEFER; its places below the end get void records, its staged records go
-// again next round and the local step skips it until then).  arrays: the lane-per-env body (its scalars in
+// segments, each env's records for one destination as a contiguous group (its updates in emission order,
+// then its request, as sfl_part.h env_groups lays them out) -- a block reserves its range per destination with
+// one global atomic, and inside that range the groups stand in env order in every destination: a wavefront places
+// its envs' groups one destination at a time (prefix sums over the lanes), the wavefronts' totals are summed in
+// LDS -- and add the launch totals of the envs that ran into P->sums.  A segment holds k_msg records this round: an
+// env with a group that reaches past that place is deferred whole (F_DEFER; its places below the end get void
+// records, its staged records go again next round and the local step skips it until then).  The same order in
+// every destination is what lets a round with deferrals still send something: the block's first env with records
+// is the first in each of its destinations' ranges.  (Places taken with one LDS atomic per group gave an env an
+// early place in the destination its lane reserved first and a late one in the next: with two destinations per env
+// and k_msg below the demand every env of a block could be deferred, every round, with the segments full of void
+// records -- tests/_segments.py, case w2-e64 at k = 17.)  arrays: the lane-per-env body (its scalars in
 // the SflState / SflPart arrays), else the wave kernels' per-env blocks (eblk).
 #ifndef SFL_COMPACT_BLOCK
 #define SFL_COMPACT_BLOCK 256  // threads (envs) per block of k_part_compact (64: -1.3 % on the 8-rank rehearsal)
@@ -112,13 +118,14 @@ __global__ void __launch_bounds__(SFL_COMPACT_BLOCK) k_part_compact(const sfl::S
   constexpr int R = sfl::PART_GROUP_MAX;  // (register arrays: the loops over them are unrolled)
   constexpr int EARLY = 2;                // update records read with the env's words (most envs stage <= 2)
   constexpr int S_LDS = 1024;             // switches whose owners the block copies to LDS (more: read from the map)
-  __shared__ uint32_t lmsg[256], bmsg[256];
-  __shared__ int32_t lown[S_LDS];
   constexpr int NWV = SFL_COMPACT_BLOCK / 64;  // waves per block
+  __shared__ uint32_t wtot[NWV][256], bmsg[256];  // a wave's records per destination (then: those of the waves before it)
+  __shared__ int32_t lown[S_LDS];
   __shared__ unsigned long long lsum[NWV][4];
   __shared__ uint32_t lopen, ldefer;
   const int world = P->world, S = P->n_sw;
-  for (int i = threadIdx.x; i < world; i += blockDim.x) lmsg[i] = 0u;
+  for (int w = 0; w < NWV; ++w)
+    for (int i = threadIdx.x; i < world; i += blockDim.x) wtot[w][i] = 0u;
   if (threadIdx.x == 0) lopen = ldefer = 0u;
   for (int i = threadIdx.x; i < S && i < S_LDS; i += blockDim.x) lown[i] = P->owner[i];
   const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -143,13 +150,60 @@ __global__ void __launch_bounds__(SFL_COMPACT_BLOCK) k_part_compact(const sfl::S
     nu = eb ? eb[sfl::EB_UPD_N] : P->upd_n[e];
   }
   __syncthreads();  // (lown)
-  if (valid) {
-    auto own = [&](int sw) { return sw < S_LDS ? lown[sw] : P->owner[sw]; };
+  auto own = [&](int sw) { return sw < S_LDS ? lown[sw] : P->owner[sw]; };
 #pragma unroll
-    for (int r = 0; r < R - 1; ++r)
-      if ((uint32_t)r < nu) dst[r] = own((r < EARLY ? early[r].port : ust[r].port) >> 2);
-    // each group takes its places in the block's range of its destination (LDS atomics)
-    n = sfl::env_groups(rd, nu, dst, pos, size, place, [&](int d, uint32_t z) { return atomicAdd(&lmsg[d], z); });
+  for (int r = 0; r < R; ++r) {
+    dst[r] = -1;
+    if ((uint32_t)r < nu) dst[r] = own((r < EARLY ? early[r].port : ust[r].port) >> 2);  // (nu <= R - 1)
+    else if ((uint32_t)r == nu && rd >= 0) dst[r] = rd;
+    pos[r] = size[r] = place[r] = 0u;
+  }
+  n = valid ? nu + (rd >= 0 ? 1u : 0u) : 0u;
+  // the wave places its groups one destination at a time, lowest first (every lane takes part: the loop is
+  // wave-uniform): a group's place in the wave's range = the records of the lanes before it for that destination
+  const int wv = threadIdx.x >> 6;
+  const unsigned long long below = (1ull << (threadIdx.x & 63)) - 1ull;
+  auto place_groups = [&](int dcur) {  // the wave's groups for destination dcur (wave-uniform)
+    uint32_t mk = 0u;
+#pragma unroll
+    for (int q = 0; q < R; ++q) mk |= dst[q] == dcur ? (1u << q) : 0u;  // (dst is -1 past the env's records)
+    const uint32_t z = (uint32_t)__builtin_popcount(mk);  // (<= 17: five bits)
+    uint32_t before = 0u, total = 0u;
+#pragma unroll
+    for (int b = 0; b < 5; ++b) {
+      const unsigned long long has = __ballot((z >> b) & 1u);
+      before += (uint32_t)__popcll(has & below) << b;
+      total += (uint32_t)__popcll(has) << b;
+    }
+    if ((threadIdx.x & 63) == 0) wtot[wv][dcur] = total;
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      if ((mk >> q) & 1u) {
+        pos[q] = (uint32_t)__builtin_popcount(mk & ((1u << q) - 1u));
+        size[q] = z;
+        place[q] = before + pos[q];
+      }
+    }
+  };
+  if (world <= 64) {  // the wave's destinations as one mask: one reduction, then a scalar loop over its bits
+    unsigned long long dm = 0ull;
+#pragma unroll
+    for (int q = 0; q < R; ++q) dm |= dst[q] >= 0 ? 1ull << ((uint32_t)dst[q] & 63u) : 0ull;
+    for (int off = 32; off > 0; off >>= 1) dm |= __shfl_xor(dm, off, 64);
+    uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)dm), hi = __builtin_amdgcn_readfirstlane((uint32_t)(dm >> 32));
+    for (; lo; lo &= lo - 1u) place_groups(__builtin_ctz(lo));
+    for (; hi; hi &= hi - 1u) place_groups(32 + __builtin_ctz(hi));
+  } else {
+    int last = -1;
+    while (true) {  // the lowest destination above the last one placed
+      int dcur = 0x7FFFFFFF;
+#pragma unroll
+      for (int q = 0; q < R; ++q) dcur = dst[q] > last && dst[q] < dcur ? dst[q] : dcur;
+      for (int off = 32; off > 0; off >>= 1) dcur = min(dcur, __shfl_xor(dcur, off, 64));
+      if (dcur == 0x7FFFFFFF) break;
+      place_groups(dcur);
+      last = dcur;
+    }
   }
   // the launch totals of the envs that ran (a deferred env sat the local step out: its totals are the
   // last round's, already counted): wave sums, then one LDS slot per wave
@@ -172,7 +226,17 @@ __global__ void __launch_bounds__(SFL_COMPACT_BLOCK) k_part_compact(const sfl::S
     lsum[w][3] = o;
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < world; i += blockDim.x) bmsg[i] = lmsg[i] ? atomicAdd(P->cnt + i, lmsg[i]) : 0u;
+  // per destination: each wave's range behind those of the waves before it, and the block's range in the segment
+  for (int i = threadIdx.x; i < world; i += blockDim.x) {
+    uint32_t acc = 0u;
+#pragma unroll
+    for (int w = 0; w < NWV; ++w) {
+      const uint32_t t = wtot[w][i];
+      wtot[w][i] = acc;
+      acc += t;
+    }
+    bmsg[i] = acc ? atomicAdd(P->cnt + i, acc) : 0u;
+  }
   if (threadIdx.x < 4) {
     unsigned long long t = 0;
 #pragma unroll
@@ -189,7 +253,7 @@ __global__ void __launch_bounds__(SFL_COMPACT_BLOCK) k_part_compact(const sfl::S
   bool fits = valid;
 #pragma unroll
   for (int r = 0; r < R; ++r)
-    if ((uint32_t)r < n && bmsg[dst[r]] + place[r] >= k) fits = false;
+    if ((uint32_t)r < n && bmsg[dst[r]] + wtot[wv][dst[r]] + place[r] >= k) fits = false;
   const bool deferred = valid && !fits;
   const bool open = valid && (rd >= 0 || deferred);
   const uint32_t n_open = __popcll(__ballot(open)), n_def = __popcll(__ballot(deferred));
@@ -232,7 +296,7 @@ __global__ void __launch_bounds__(SFL_COMPACT_BLOCK) k_part_compact(const sfl::S
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     if ((uint32_t)r >= n) continue;
-    const uint32_t at = bmsg[dst[r]] + place[r];
+    const uint32_t at = bmsg[dst[r]] + wtot[wv][dst[r]] + place[r];
     sfl::PartMsg* x = P->msg_out + (size_t)dst[r] * (k + 1) + 1 + at;
     if (fits) {
       sfl::PartMsg y = (uint32_t)r < nu ? (r < EARLY ? early[r] : ust[r]) : sfl::msg_of_req(req);
