@@ -41,6 +41,9 @@
  *   sfl_curve_begin / sfl_curve_read   the per-episode record learn() returns (cum_reward, arrived_trains,
  *                     num_malfunctions, delays: distr_q.py:346-366) for sfl_step, reduced on the device into
  *                     learning curves per episode bin and env series instead of [episode][env] host arrays
+ *   sfl_create_eval / sfl_bank_eval   DistrQLearning.load + test (distr_q.py:510-527, 184-241) as eval.py runs them
+ *                     (eval.py:85-97), for a bank of tables shared by many seeded envs: one greedy episode per env,
+ *                     the per-table arrival statistics reduced on the device
  *   sfl_get_phase_cycles  the per-phase time accumulators            switchfl/switch_env.py:67-73
  *                     (flatland_step_time, last_time, action_selection_time, update_time, reset_time ...)
  */
@@ -482,6 +485,78 @@ int sfl_curve_exploit(sfl_handle* h, int32_t exploit_freq);
 int sfl_curve_read_exploit(sfl_handle* h, sfl_curve_xcell* out /* [n_bins][n_series] */);
 int sfl_curve_rounds(sfl_handle* h, int32_t* out /* [n_envs] */);
 int sfl_curve_exploit_fold_ms(sfl_handle* h, double* last_ms, double* total_ms /* either may be NULL */);
+
+/* ---- policy-bank evaluation: P shared Q-tables, one greedy episode per env, reduced on the device ----
+ * The reference evaluates a trained table with DistrQLearning.test (distr_q.py:184-241) in a one-env process, a few
+ * runs per experiment (eval.py:85-97).  sfl_test does the same per env of a handle, but every env carries a private
+ * copy of its table.  An evaluation handle (sfl_create_eval) instead owns a read-only bank of n_policies tables, each
+ * in the layout of sfl_get_q; sfl_bank_eval runs one greedy episode per env, env e on table env_policy[e] and on its
+ * own seed, and reduces the episodes into one sfl_eval_cell per table on the device.
+ *   sfl_create_eval allocates what sfl_create does except the per-env Q block and key set, plus the bank:
+ *     [n_policies][q_per_env] doubles and [n_policies][touched_words] words.  Every table starts as default_q with an
+ *     empty key set and counts as unset until sfl_bank_set or sfl_bank_copy fills it.  The kernel is chosen as in
+ *     sfl_create (SFL_WAVE_G, SFL_LDS_MAP, SFL_KERNEL; sfl_get_kernel_note); the row with the map tables in LDS runs
+ *     its own evaluation kernel (a launch is a whole episode).  hp's epsilon / lr keys are unused.  n_policies == 0
+ *     is refused.
+ *   sfl_bank_set / sfl_bank_get move table p between host and device (q or touched may be NULL to skip one);
+ *     sfl_bank_copy copies device to device from a training handle on the same device: kind SFL_BANK_FROM_ENV env
+ *     `index`'s table and key set, SFL_BANK_FROM_COHORT consensus cohort `index`'s (sfl_consensus).  Refused when
+ *     q_per_env, rows_per_env or default_q differ, the devices differ, src is an evaluation handle or
+ *     graph-partitioned, or there is no such env / cohort.
+ *   sfl_bank_eval starts every env from a reset, so a second call replays the same episodes unless the tables or
+ *     env_policy changed.  Every pointer of sfl_eval_out is an optional host array.  Refused when an entry of
+ *     env_policy is >= n_policies or names a table that was never set.  The handle's counters (sfl_get_counters)
+ *     report the launch's decisions, ticks and kernel ms.
+ *   The bank is READ-ONLY during an evaluation.  The reference's test() adds every row it looks up to the Q dict
+ *     (max_action's __check_entry, and so does sfl_test to the env's key set); sfl_bank_eval records none: the key
+ *     sets stay as they were set.  A compact row outside a key set already holds default_q, so the greedy choice, and
+ *     with it every output, is the same as sfl_test's on a private copy of the table.
+ *   sfl_bank_read: the cells of the last sfl_bank_eval, [n_policies] (refused before the first successful one).
+ *     Every field is an integer (cum_reward is an exact integer in its double), so a cell does not depend on the
+ *     order the envs were folded in.  The per-train
+ *     rule is the train-arrival table's of the reference's notebook (plot.ipynb cell 15), by train handle: at its
+ *     destination (at_dest) with delay <= 0 is early, at its destination with delay > 0 late, anything else not
+ *     arrived; a train that did not arrive carries a delay too, which is not part of delay_sum_arrived.  (`arrived`,
+ *     the reference's arrived_trains counter, is counted at the switches and can be below the at_dest count.)
+ *     A table no env followed has episodes == 0, its min fields INT64_MAX and its max fields INT64_MIN.
+ *   sfl_bank_fold_ms: the device time of the last fold and of all folds since create (0 on the host build; never
+ *     part of sfl_counters.last_kernel_ms).
+ *   An evaluation handle has no learner and no per-env table: sfl_learn_begin, sfl_apply_qinit, sfl_learn, sfl_test,
+ *     sfl_step, sfl_get_q, sfl_set_q, sfl_consensus, sfl_curve_begin, sfl_part_config, sfl_env_begin /
+ *     sfl_env_begin_wave and sfl_set_hparam_groups fail on it with "evaluation handle" in the message.
+ *     sfl_get_env_state, sfl_get_counters, sfl_get_kernel_note, sfl_set_mf_schedule and sfl_set_stream work as on any
+ *     handle. */
+typedef struct {            /* one policy's cell: 15 x int64 */
+  int64_t episodes;         /* envs that followed the table in the last sfl_bank_eval */
+  int64_t trains_early, trains_late, trains_not_arrived;   /* over those episodes' T trains each */
+  int64_t arrived_min, arrived_max;
+  int64_t all_arrived;      /* episodes with arrived == T */
+  int64_t reward_sum, reward_min, reward_max;   /* cum_reward, an exact integer */
+  int64_t decisions_sum, ticks_sum, malfunctions_sum;
+  int64_t delay_sum_arrived;  /* sum of the delays of the trains that arrived */
+  int64_t truncated;        /* episodes with decisions > max_steps */
+} sfl_eval_cell;
+typedef struct {            /* optional host outputs of sfl_bank_eval */
+  double* cum_reward;       /* [n_envs] */
+  int32_t* arrived;         /* [n_envs] */
+  int32_t* malfunctions;    /* [n_envs] */
+  int32_t* decisions;       /* [n_envs] */
+  int32_t* ticks;           /* [n_envs] */
+  int32_t* truncated;       /* [n_envs] 1: the episode ended by max_steps */
+  int32_t* delays;          /* [T][n_envs] train_to_last_node delays */
+  uint8_t* at_dest;         /* [T][n_envs] 1: the train stands at its destination at the episode's end (its state is
+                               DONE): the trains_at_dest the reference's test() saves (distr_q.py:237-239) */
+} sfl_eval_out;
+#define SFL_BANK_FROM_ENV    0
+#define SFL_BANK_FROM_COHORT 1
+int sfl_create_eval(const sfl_map_desc* map, const sfl_hparams* hp, uint32_t n_envs, const uint64_t* env_seeds,
+                    int device, uint32_t n_policies, sfl_handle** out);
+int sfl_bank_set(sfl_handle* h, uint32_t p, const double* q /* [q_per_env] */, const uint32_t* touched);
+int sfl_bank_get(sfl_handle* h, uint32_t p, double* q, uint32_t* touched);
+int sfl_bank_copy(sfl_handle* h, uint32_t p, sfl_handle* src, int32_t kind, uint32_t index);
+int sfl_bank_eval(sfl_handle* h, const uint32_t* env_policy /* [n_envs] */, sfl_eval_out* out /* may be NULL */);
+int sfl_bank_read(sfl_handle* h, sfl_eval_cell* out /* [n_policies] */);
+int sfl_bank_fold_ms(sfl_handle* h, double* last_ms, double* total_ms /* either may be NULL */);
 #ifdef __cplusplus
 }
 #endif

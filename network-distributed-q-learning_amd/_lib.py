@@ -63,6 +63,12 @@ CURVE_FIELDS = ("count", "lost", "arrived_sum", "arrived_min", "arrived_max", "a
 # include/sfl.h sfl_curve_xcell: the 11 int64 words of an exploit cell in order
 CURVE_XFIELDS = ("count", "lost", "arrived_sum", "arrived_min", "arrived_max", "all_arrived", "reward_sum", "reward_min",
                  "reward_max", "first_episode", "last_episode")
+# include/sfl.h sfl_eval_cell: the 15 int64 words of a policy's cell in order, and SFL_BANK_FROM_*
+EVAL_FIELDS = ("episodes", "trains_early", "trains_late", "trains_not_arrived", "arrived_min", "arrived_max", "all_arrived",
+               "reward_sum", "reward_min", "reward_max", "decisions_sum", "ticks_sum", "malfunctions_sum",
+               "delay_sum_arrived", "truncated")
+BANK_FROM_ENV = 0
+BANK_FROM_COHORT = 1
 CURVE_MAX_TABLE_BYTES = 64 << 20
 CURVE_MAX_RING_BYTES = 1 << 30
 
@@ -89,6 +95,13 @@ class EnvIO(C.Structure):
                 ("state", P(C.c_uint32)), ("mask", P(C.c_uint32)), ("reward", P(C.c_int32)), ("now", P(C.c_int32)),
                 ("next_switch", P(C.c_int32)), ("step_now", P(C.c_int32)), ("arrived", P(C.c_uint32)),
                 ("malfunctions", P(C.c_int32)), ("delays", P(C.c_int32)), ("truncated", P(C.c_int32))]
+
+
+class EvalOut(C.Structure):
+    """sfl_eval_out: the optional per-env outputs of sfl_bank_eval."""
+    _fields_ = [("cum_reward", P(C.c_double)), ("arrived", P(C.c_int32)), ("malfunctions", P(C.c_int32)),
+                ("decisions", P(C.c_int32)), ("ticks", P(C.c_int32)), ("truncated", P(C.c_int32)),
+                ("delays", P(C.c_int32)), ("at_dest", P(C.c_uint8))]
 
 
 OBS_WIDTH = 18    # include/sfl.h SFL_OBS_WIDTH
@@ -161,6 +174,14 @@ EXPORTS = {
     "sfl_curve_read_exploit": (C.c_int, [C.c_void_p, P(C.c_int64)]),
     "sfl_curve_rounds": (C.c_int, [C.c_void_p, P(C.c_int32)]),
     "sfl_curve_exploit_fold_ms": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double)]),
+    # policy-bank evaluation (runtime.EvalBatch)
+    "sfl_create_eval": (C.c_int, [P(MapDesc), P(HParams), C.c_uint32, P(C.c_uint64), C.c_int, C.c_uint32, P(C.c_void_p)]),
+    "sfl_bank_set": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_double), P(C.c_uint32)]),
+    "sfl_bank_get": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_double), P(C.c_uint32)]),
+    "sfl_bank_copy": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_uint32]),
+    "sfl_bank_eval": (C.c_int, [C.c_void_p, P(C.c_uint32), P(EvalOut)]),
+    "sfl_bank_read": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "sfl_bank_fold_ms": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double)]),
 }
 
 

@@ -18,7 +18,7 @@
 #include "sfl_kwave_g.h"
 #include "sfl_wave.h"
 
-SFL_KWAVE_UNIT(Main)  // this unit's wave kernels (sflk::owner: all but variant 7's and the HPG ones)
+SFL_KWAVE_UNIT(Main)  // this unit's wave kernels (sflk::owner: all but variant 7's, the HPG, the EXT and the BANK ones)
 
 namespace {
 
@@ -717,8 +717,11 @@ struct HipBackend {
     // hyperparameter groups: the HPG instantiation, plain only (the engine refuses a trace and passes no phase
     // counters on a grouped handle); k_run reads the map's group pointer at run time
     const bool hpg = m.env_group != nullptr;
+    // policy-bank evaluation (sfl_bank_eval): the BANK instantiation; k_run reads the map's bank pointer at run time
+    const bool bank = c.mode == sfl::MODE_BANK;
     if (variant >= 1 && variant < sfl::kNumVariants)
-      sflk::launch({variant, hpg ? sflk::Mode::Hpg : c.trace ? sflk::Mode::Trace : c.phase_cyc ? sflk::Mode::Timed : sflk::Mode::Plain,
+      sflk::launch({variant,
+                    bank ? sflk::Mode::Bank : hpg ? sflk::Mode::Hpg : c.trace ? sflk::Mode::Trace : c.phase_cyc ? sflk::Mode::Timed : sflk::Mode::Plain,
                     s.E, stream, pm, ps, pc});
     else if (m.T <= 32) k_run<1><<<blocks, 256, 0, stream>>>(pm, ps, pc);
     else if (m.T <= 64) k_run<2><<<blocks, 256, 0, stream>>>(pm, ps, pc);
@@ -829,6 +832,19 @@ struct HipBackend {
     float t = 0.f;
     hipEventElapsedTime(&t, ev1, ev2);
     return t;
+  }
+  // sfl_bank_eval: the kernels of sfl_eval.hip queued on the handle's stream between the two events (elapsed_ms()
+  // after the caller's sync is the fold's time)
+  int eval_fold(const sfl::EvalArgs& a) {
+    check(hipEventRecord(ev0, stream), "event");
+    const char* what = "";
+    int code = 0;
+    if (sfl::eval_launch(a, (void*)stream, &what, &code)) {
+      if (err.empty()) err = std::string(what) + ": " + hipGetErrorString((hipError_t)code);
+      return -1;
+    }
+    check(hipEventRecord(ev1, stream), "event");
+    return err.empty() ? 0 : -1;
   }
   int sync() { return check(stream_wait(), "sync") && err.empty() ? 0 : -1; }
   // process-wide, one per device, built on first use and kept for the life of the process

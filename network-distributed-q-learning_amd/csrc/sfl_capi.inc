@@ -35,6 +35,20 @@ int sfl_create(const sfl_map_desc* map, const sfl_hparams* hp, uint32_t n_envs, 
   return rc;
 }
 
+int sfl_create_eval(const sfl_map_desc* map, const sfl_hparams* hp, uint32_t n_envs, const uint64_t* env_seeds, int device,
+                    uint32_t n_policies, sfl_handle** out) {
+  if (n_policies == 0) return sfl::fail("sfl_create_eval: n_policies must be at least 1");
+  H* h = nullptr;
+  int rc = sfl::create<Backend>(map, hp, n_envs, env_seeds, device, &h, n_policies);
+  if (rc == 0) *out = reinterpret_cast<sfl_handle*>(h);
+  return rc;
+}
+
+// an evaluation handle (sfl_create_eval) has no learner and no per-env table
+static int no_eval(H* h, const char* fn, const char* why) {
+  return h->bank.on ? sfl::fail(std::string(fn) + ": an evaluation handle " + why + " (sfl_create_eval)") : 0;
+}
+
 int sfl_destroy(sfl_handle* h) {
   delete HH(h);
   return 0;
@@ -48,6 +62,7 @@ int sfl_learn_begin(sfl_handle* h, const uint64_t* rng_states) {
 int sfl_apply_qinit(sfl_handle* h, uint32_t n_rows, const uint32_t* row_port, const uint32_t* row_state,
                     const double* values) {
   if (!h) return sfl::fail("sfl_apply_qinit: null handle");
+  if (int rc = no_eval(HH(h), "sfl_apply_qinit", "has no per-env table")) return rc;
   if (HH(h)->part.world) return sfl::part_qinit(HH(h), n_rows, row_port, row_state, values);
   return sfl::apply_qinit(HH(h), n_rows, row_port, row_state, values);
 }
@@ -60,6 +75,7 @@ static int count_launch(H*) { return 0; }
 int sfl_learn(sfl_handle* h, sfl_run_args* args) {
   if (!h || !args) return sfl::fail("sfl_learn: null argument");
   H* hh = HH(h);
+  if (int rc = no_eval(hh, "sfl_learn", "has no learner")) return rc;
   std::vector<int32_t> ept(hh->E);
   hh->be.d2h(ept.data(), hh->st.ep_t, hh->E * 4);
   hh->be.sync();
@@ -78,6 +94,7 @@ int sfl_learn(sfl_handle* h, sfl_run_args* args) {
 int sfl_test(sfl_handle* h, sfl_run_args* args) {
   if (!h || !args) return sfl::fail("sfl_test: null argument");
   H* hh = HH(h);
+  if (int rc0 = no_eval(hh, "sfl_test", "has no per-env table; use sfl_bank_eval")) return rc0;
   int rc = sfl::test_begin(hh);
   if (rc) return rc;
   sfl::SflCtl c{};
@@ -96,6 +113,7 @@ int sfl_test(sfl_handle* h, sfl_run_args* args) {
 int sfl_step(sfl_handle* h, int64_t decisions_per_env, uint64_t* decisions_done, double* kernel_ms) {
   if (!h || decisions_per_env <= 0) return sfl::fail("sfl_step: bad argument");
   H* hh = HH(h);
+  if (int rc0 = no_eval(hh, "sfl_step", "has no learner")) return rc0;
   sfl::SflCtl c{};
   c.mode = 0;
   c.exploit_freq = hh->cv.x_on ? hh->cv.x_freq : 0;  // greedy rounds only with an exploit record (sfl_curve_exploit)
@@ -110,6 +128,7 @@ int sfl_step(sfl_handle* h, int64_t decisions_per_env, uint64_t* decisions_done,
 
 int sfl_get_q(sfl_handle* h, uint32_t env, double* q, uint32_t* touched) {
   H* hh = HH(h);
+  if (int rc = no_eval(hh, "sfl_get_q", "has no per-env table; use sfl_bank_get")) return rc;
   if (env >= hh->E) return sfl::fail("sfl_get_q: env out of range");
   if (hh->part.world) return sfl::fail("sfl_get_q: the handle is graph-partitioned (use sfl_part_get_q)");
   if (q) hh->be.d2h(q, hh->st.q + (size_t)env * hh->map.q_per_env, hh->map.q_per_env * 8);
@@ -119,6 +138,7 @@ int sfl_get_q(sfl_handle* h, uint32_t env, double* q, uint32_t* touched) {
 
 int sfl_set_q(sfl_handle* h, uint32_t env, const double* q, const uint32_t* touched) {
   H* hh = HH(h);
+  if (int rc = no_eval(hh, "sfl_set_q", "has no per-env table; use sfl_bank_set")) return rc;
   if (env >= hh->E) return sfl::fail("sfl_set_q: env out of range");
   if (hh->part.world) return sfl::fail("sfl_set_q: the handle is graph-partitioned");
   if (q) hh->be.h2d(hh->st.q + (size_t)env * hh->map.q_per_env, q, hh->map.q_per_env * 8);
@@ -361,6 +381,40 @@ int sfl_curve_exploit_fold_ms(sfl_handle* h, double* last_ms, double* total_ms) 
 int sfl_curve_end(sfl_handle* h) {
   if (!h) return sfl::fail("sfl_curve_end: null handle");
   return sfl::curve_end(HH(h));
+}
+
+// ---- policy-bank evaluation (sfl_eval.h) ----
+int sfl_bank_set(sfl_handle* h, uint32_t p, const double* q, const uint32_t* touched) {
+  if (!h) return sfl::fail("sfl_bank_set: null handle");
+  return sfl::bank_set(HH(h), p, q, touched);
+}
+
+int sfl_bank_get(sfl_handle* h, uint32_t p, double* q, uint32_t* touched) {
+  if (!h) return sfl::fail("sfl_bank_get: null handle");
+  return sfl::bank_get(HH(h), p, q, touched);
+}
+
+int sfl_bank_copy(sfl_handle* h, uint32_t p, sfl_handle* src, int32_t kind, uint32_t index) {
+  if (!h) return sfl::fail("sfl_bank_copy: null handle");
+  return sfl::bank_copy(HH(h), p, HH(src), kind, index);
+}
+
+int sfl_bank_eval(sfl_handle* h, const uint32_t* env_policy, sfl_eval_out* out) {
+  if (!h) return sfl::fail("sfl_bank_eval: null handle");
+  return sfl::bank_eval(HH(h), env_policy, out);
+}
+
+int sfl_bank_read(sfl_handle* h, sfl_eval_cell* out) {
+  if (!h) return sfl::fail("sfl_bank_read: null handle");
+  return sfl::bank_read(HH(h), out);
+}
+
+int sfl_bank_fold_ms(sfl_handle* h, double* last_ms, double* total_ms) {
+  if (!h) return sfl::fail("sfl_bank_fold_ms: null handle");
+  if (!HH(h)->bank.on) return sfl::fail("sfl_bank_fold_ms: not an evaluation handle (sfl_create_eval)");
+  if (last_ms) *last_ms = HH(h)->bank.last_ms;
+  if (total_ms) *total_ms = HH(h)->bank.total_ms;
+  return 0;
 }
 
 }  // extern "C"

@@ -115,6 +115,11 @@ struct SflMap {
   const double* hpg_eps_tab;  // [n_groups][ntab]
   const double* hpg_lr_tab;   // [n_groups][ntab]
   const double* hpg_sc;       // [n_groups][4]: HPG_EPS0, HPG_EPS_DECAY, HPG_LR0, HPG_LR_DECAY
+  // policy bank (sfl_create_eval / sfl_bank_eval): P read-only Q-tables [P][q_per_env] shared by the
+  // envs of an evaluation handle, env e following table bank_policy[e].  null on every other handle.  Such a handle
+  // has no per-env table or key set (SflState::q and touched are null), and a greedy run inserts no key-set row.
+  const double* bank_q;
+  const uint32_t* bank_policy;  // [E], the table each env follows in the current sfl_bank_eval
 };
 enum : int { HPG_EPS0 = 0, HPG_EPS_DECAY = 1, HPG_LR0 = 2, HPG_LR_DECAY = 3 };
 
@@ -199,7 +204,7 @@ struct SflState {
 };
 
 struct SflCtl {
-  int32_t mode;          // 0 = learn, 1 = greedy test
+  int32_t mode;          // 0 = learn, 1 = greedy test, MODE_BANK = a greedy test on the policy bank (SflMap::bank_q)
   int32_t exploit_freq;  // learn: greedy round before episode t when (t+1) % f == 0
   int32_t ep_target;     // stop once this many episodes of the mode are done (-1: unlimited)
   int32_t stats_cap;     // rows in the stats buffers: row = (episode index - stats_base) % cap
@@ -222,7 +227,13 @@ struct SflCtl {
   int32_t trace_cap;
   const struct SflExt* ext;  // external-action mode (mode 2) buffers, device memory; null otherwise
   uint64_t* phase_cyc;       // [8] per-phase cycles of sampled wavefronts (learn / test launches), or null
+  // MODE_BANK: besides row 0 of the st_* buffers (stats_cap = 1), per train whether it stands at its destination at the
+  // episode's end (its state is DONE: the trains_at_dest the reference's test() saves, distr_q.py:237-239), beside its
+  // delay, and per env whether the episode ended by truncation (its decisions exceed max_steps)
+  uint8_t* ev_at_dest;       // [T][E]
+  int32_t* ev_trunc;         // [E]
 };
+enum : int32_t { MODE_BANK = 3 };
 
 // External-action mode (sfl_env_step): the env alone, stepped one decision per call by a policy on the
 // host -- the PettingZoo AEC protocol agent_iter / last / step(action) / observe (switch_env.py:616-675)
@@ -571,9 +582,13 @@ struct Env {
   // Q-table --------------------------------------------------------------------
   SFL_FN double* qrow(int sw, int slot, uint32_t state) const {
     const int g = 4 * sw + slot;
-    return s.q + (size_t)e * m.q_per_env + m.q_off[g] + (size_t)state * m.q_w[g];
+    // (an evaluation handle: the env's table of the bank, which is never written -- env_run posts nothing when greedy)
+    double* base = m.bank_q ? const_cast<double*>(m.bank_q) + (size_t)m.bank_policy[e] * m.q_per_env
+                            : s.q + (size_t)e * m.q_per_env;
+    return base + m.q_off[g] + (size_t)state * m.q_w[g];
   }
   SFL_FN void touch(int sw, int slot, uint32_t state) const {
+    if (m.bank_q) return;  // the bank is read-only: a greedy run's key-set inserts (max_action's __check_entry) are not recorded
     const uint32_t row = m.row_base[4 * sw + slot] + state;
     s.touched[(size_t)e * m.touched_words + (row >> 5)] |= 1u << (row & 31u);
   }
@@ -1291,7 +1306,7 @@ SFL_FN void env_run(const SflMap& m, const SflState& s, const SflCtl& c, uint32_
   d.sw = d.h = d.slot = d.action = d.j = d.reward = d.next_sw = 0;
   d.state = 0;
   double cum = s.cum_reward[e];
-  const bool test_mode = c.mode == 1;
+  const bool test_mode = c.mode == 1 || c.mode == MODE_BANK;
   v.masks_load();
   while (true) {
     const bool busy = wave_any(phase == PH_DECIDE || phase == PH_POST);
@@ -1363,6 +1378,9 @@ SFL_FN void env_run(const SflMap& m, const SflState& s, const SflCtl& c, uint32_
             c.st_ticks[row * s.E + e] = s.ep_ticks[e];
             for (int h = 0; h < m.T; ++h) c.st_delays[(row * m.T + h) * s.E + e] = s.tr_delay[v.ix(h)];
           }
+          if (c.ev_at_dest)
+            for (int h = 0; h < m.T; ++h) c.ev_at_dest[(size_t)h * s.E + e] = tb_state(s.tr_bits[v.ix(h)]) == S_DONE ? 1 : 0;
+          if (c.ev_trunc) c.ev_trunc[e] = (int64_t)s.ep_dec[e] > m.max_steps ? 1 : 0;
           s.n_test[e] += 1;
         } else {
           const int32_t i = s.ep_t[e];

@@ -17,6 +17,7 @@
 #include "sfl_consensus.h"
 #include "sfl_core.h"
 #include "sfl_curve.h"
+#include "sfl_eval.h"
 #include "sfl_mfgen.h"
 #include "sfl_part.h"
 
@@ -101,6 +102,24 @@ struct Handle {
     float x_last_ms = 0.f;
     double x_total_ms = 0.0;
   } cv;
+  // policy-bank evaluation (sfl_create_eval / sfl_bank_*; sfl_eval.h): on an evaluation handle st.q and
+  // st.touched are null and map.bank_q / map.bank_policy point at q / policy below.  set[p]: table p was filled;
+  // the per-env outputs of the last episode launch ([E], delays and at_dest [T][E]) and the cells the fold made of them
+  struct Bank {
+    bool on = false;
+    uint32_t P = 0;
+    double* q = nullptr;         // [P][q_per_env]
+    uint32_t* keys = nullptr;    // [P][touched_words]
+    std::vector<uint8_t> set;
+    uint32_t* policy = nullptr;  // [E]
+    double* cum = nullptr;
+    int32_t *arrived = nullptr, *mf = nullptr, *dec = nullptr, *ticks = nullptr, *trunc = nullptr, *delays = nullptr;
+    uint8_t* at_dest = nullptr;
+    int64_t* cells = nullptr;    // [P][EV_WORDS]
+    bool folded = false;
+    float last_ms = 0.f;
+    double total_ms = 0.0;
+  } bank;
 
   template <class T>
   T* dalloc(size_t n) {
@@ -240,19 +259,22 @@ inline int wave64_variant(int S, int T) {
   return 0;
 }
 
+// n_policies > 0: an evaluation handle (sfl_create_eval) -- no per-env Q block and key set, a bank of n_policies tables
 template <class B>
 int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const uint64_t* env_seeds, int device,
-           Handle<B>** out) {
-  if (!md || !hp || !out || n_envs == 0) return fail("sfl_create: null argument or zero envs");
-  if (md->T > 32 * MAXW) return fail("sfl_create: at most 128 trains per env");
-  if (md->S * 4 >= 0xFFFF) return fail("sfl_create: too many switches");
-  if (md->K < 1 || md->K > 341) return fail("sfl_create: station count out of range");
-  if (md->delay_threshold < -65536 || md->delay_threshold > 65536) return fail("sfl_create: delay_threshold out of range");
+           Handle<B>** out, uint32_t n_policies = 0) {
+  const std::string fn = n_policies ? "sfl_create_eval" : "sfl_create";  // (the entry point the messages name)
+  if (!md || !hp || !out || n_envs == 0) return fail(fn + ": null argument or zero envs");
+  if (md->T > 32 * MAXW) return fail(fn + ": at most 128 trains per env");
+  if (md->S * 4 >= 0xFFFF) return fail(fn + ": too many switches");
+  if (md->K < 1 || md->K > 341) return fail(fn + ": station count out of range");
+  if (md->delay_threshold < -65536 || md->delay_threshold > 65536) return fail(fn + ": delay_threshold out of range");
   auto* h = new Handle<B>();
   h->device = device;
   if (int rc = h->be.init(device)) {
+    const std::string why = h->be.error();
     delete h;
-    return fail(std::string("sfl_create: backend init failed: ") + h->be.error());
+    return fail(fn + ": backend init failed: " + why);
   }
   h->E = n_envs;
   h->h_sw_np.assign(md->sw_np, md->sw_np + md->S);
@@ -423,7 +445,7 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
     }
     if (!pack_ok) {
       delete h;
-      return fail("sfl_create: compact Q columns do not follow action order (map compiler mismatch)");
+      return fail(fn + ": compact Q columns do not follow action order (map compiler mismatch)");
     }
     h->keep.push_back(std::move(swp));
     m.sw_pack = h->upload(h->keep.back().data(), h->keep.back().size());
@@ -483,8 +505,29 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
   s.sem = h->template dalloc<uint64_t>(NP * E);
   s.slot = h->template dalloc<uint64_t>(S * T * E);
   s.counts = h->template dalloc<uint32_t>(S * E);
-  s.q = h->template dalloc<double>((size_t)m.q_per_env * E);
-  s.touched = h->template dalloc<uint32_t>((size_t)m.touched_words * E);
+  typename Handle<B>::Bank& bk = h->bank;
+  bk.on = n_policies > 0;
+  if (!bk.on) {
+    s.q = h->template dalloc<double>((size_t)m.q_per_env * E);
+    s.touched = h->template dalloc<uint32_t>((size_t)m.touched_words * E);
+  } else {
+    bk.P = n_policies;
+    bk.set.assign(n_policies, 0);
+    bk.q = h->template dalloc<double>((size_t)m.q_per_env * n_policies);
+    bk.keys = h->template dalloc<uint32_t>((size_t)m.touched_words * n_policies);
+    bk.policy = h->template dalloc<uint32_t>(E);
+    bk.cum = h->template dalloc<double>(E);
+    bk.arrived = h->template dalloc<int32_t>(E);
+    bk.mf = h->template dalloc<int32_t>(E);
+    bk.dec = h->template dalloc<int32_t>(E);
+    bk.ticks = h->template dalloc<int32_t>(E);
+    bk.trunc = h->template dalloc<int32_t>(E);
+    bk.delays = h->template dalloc<int32_t>(T * E);
+    bk.at_dest = h->template dalloc<uint8_t>(T * E);
+    bk.cells = h->template dalloc<int64_t>((size_t)n_policies * EV_WORDS);
+    m.bank_q = bk.q;
+    m.bank_policy = bk.policy;
+  }
   h->d_launch_dec = h->template dalloc<uint64_t>(E);
   h->d_launch_ticks = h->template dalloc<uint64_t>(E);
   h->d_launch_bytes = h->template dalloc<uint64_t>(E);
@@ -493,11 +536,11 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
   for (void* p : h->allocs)
     if (!p) {
       delete h;
-      return fail("sfl_create: device allocation failed");
+      return fail(fn + ": device allocation failed");
     }
-  if (!m.grid || !s.q) {
+  if (!m.grid || (!bk.on && !s.q) || (bk.on && !bk.q)) {
     delete h;
-    return fail("sfl_create: device allocation failed (out of memory?)");
+    return fail(fn + ": device allocation failed (out of memory?)");
   }
   // initial values
   h->be.memset(s.phase, 0, E * 4);
@@ -530,13 +573,19 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
   h->be.memset(s.slot, 0, S * T * E * 8);
   h->be.memset(s.counts, 0, S * E * 4);
   h->be.memset(h->d_phase, 0, 8 * 8);
-  h->be.memset(s.touched, 0, (size_t)m.touched_words * E * 4);
-  h->be.fill_f64(s.q, m.default_q, (size_t)m.q_per_env * E);
+  if (!bk.on) {
+    h->be.memset(s.touched, 0, (size_t)m.touched_words * E * 4);
+    h->be.fill_f64(s.q, m.default_q, (size_t)m.q_per_env * E);
+  } else {
+    h->be.memset(bk.keys, 0, (size_t)m.touched_words * bk.P * 4);
+    h->be.fill_f64(bk.q, m.default_q, (size_t)m.q_per_env * bk.P);
+    h->be.memset(bk.policy, 0, E * 4);
+  }
   h->seeds.assign(env_seeds, env_seeds + E);
   h->be.h2d(s.seed, env_seeds, E * 8);
   if (int rc = h->be.sync()) {
     delete h;
-    return fail(std::string("sfl_create: ") + h->be.error());
+    return fail((fn + ": ") + h->be.error());
   }
   *out = h;
   return 0;
@@ -567,6 +616,7 @@ int set_mf_schedule(Handle<B>* h, int32_t steps, const uint8_t* table) {
 // Everything is validated on the host before anything is uploaded; a refused call leaves the handle as it was.
 template <class B>
 int set_hparam_groups(Handle<B>* h, int32_t n_groups, const sfl_hparam_group* groups, const uint16_t* env_group) {
+  if (h->bank.on) return fail("sfl_set_hparam_groups: an evaluation handle has no learner (sfl_create_eval)");
   if (h->part.world) return fail("sfl_set_hparam_groups: the handle is graph-partitioned");
   if (h->env_mode) return fail("sfl_set_hparam_groups: the handle is in external-action mode (no learner)");
   if (n_groups < 0 || n_groups > SFL_MAX_HPARAM_GROUPS)
@@ -629,6 +679,7 @@ int curve_exploit_sync(Handle<B>* h);
 // default_rng(seed).bit_generator.state, computed on the host.
 template <class B>
 int learn_begin(Handle<B>* h, const uint64_t* rng_states) {
+  if (h->bank.on) return fail("sfl_learn_begin: an evaluation handle has no learner (sfl_create_eval)");
   if (int rc = part_host_access(h, true)) return rc;
   const size_t E = h->E;
   std::vector<uint64_t> soa(5 * E);
@@ -756,6 +807,7 @@ int check_errors(Handle<B>* h) {
 
 template <class B>
 int run(Handle<B>* h, const SflCtl& c_in, sfl_run_args* args) {
+  if (h->bank.on) return fail("sfl_run: an evaluation handle has no per-env table (sfl_create_eval); drive it with sfl_bank_eval");
   if (h->part.world) return fail("sfl_run: the handle is graph-partitioned; drive it with sfl_part_*");
   if (h->env_mode) return fail("sfl_run: the handle is in external-action mode (sfl_env_begin); drive it with sfl_env_step");
   // (the grouped kernels are built plain only: no traced and no phase-timed instantiation)
@@ -862,6 +914,158 @@ int run(Handle<B>* h, const SflCtl& c_in, sfl_run_args* args) {
 }
 
 // ---------------------------------------------------------------------------
+// policy-bank evaluation (include/sfl.h sfl_create_eval / sfl_bank_*; sfl_eval.h)
+// ---------------------------------------------------------------------------
+template <class B>
+int bank_check(Handle<B>* h, const char* fn, uint32_t p) {
+  if (!h->bank.on) return fail(std::string(fn) + ": not an evaluation handle (sfl_create_eval)");
+  if (p >= h->bank.P) return fail(std::string(fn) + ": policy " + std::to_string(p) + " of " + std::to_string(h->bank.P));
+  return 0;
+}
+
+template <class B>
+int bank_set(Handle<B>* h, uint32_t p, const double* q, const uint32_t* touched) {
+  if (int rc = bank_check(h, "sfl_bank_set", p)) return rc;
+  const SflMap& m = h->map;
+  if (q) h->be.h2d(h->bank.q + (size_t)p * m.q_per_env, q, m.q_per_env * 8);
+  if (touched) h->be.h2d(h->bank.keys + (size_t)p * m.touched_words, touched, (size_t)m.touched_words * 4);
+  if (h->be.sync()) return fail(h->be.error());
+  h->bank.set[p] = 1;
+  return 0;
+}
+
+template <class B>
+int bank_get(Handle<B>* h, uint32_t p, double* q, uint32_t* touched) {
+  if (int rc = bank_check(h, "sfl_bank_get", p)) return rc;
+  const SflMap& m = h->map;
+  if (q) h->be.d2h(q, h->bank.q + (size_t)p * m.q_per_env, m.q_per_env * 8);
+  if (touched) h->be.d2h(touched, h->bank.keys + (size_t)p * m.touched_words, (size_t)m.touched_words * 4);
+  return h->be.sync() ? fail(h->be.error()) : 0;
+}
+
+// device to device, from a training handle on the same device (its calls are synchronous: nothing of it is in flight)
+template <class B>
+int bank_copy(Handle<B>* h, uint32_t p, Handle<B>* src, int32_t kind, uint32_t index) {
+  if (int rc = bank_check(h, "sfl_bank_copy", p)) return rc;
+  if (!src) return fail("sfl_bank_copy: null source handle");
+  if (src->bank.on) return fail("sfl_bank_copy: the source is itself an evaluation handle (use sfl_bank_get / sfl_bank_set)");
+  if (src->part.world) return fail("sfl_bank_copy: the source is graph-partitioned (its tables are owned rows)");
+  if (src->device != h->device)
+    return fail("sfl_bank_copy: the source is on device " + std::to_string(src->device) + ", the bank on device " +
+                std::to_string(h->device));
+  const SflMap &m = h->map, &sm = src->map;
+  if (sm.q_per_env != m.q_per_env || sm.rows_per_env != m.rows_per_env)
+    return fail("sfl_bank_copy: the source's Q layout differs (q_per_env " + std::to_string(sm.q_per_env) + " / " +
+                std::to_string(m.q_per_env) + ", rows_per_env " + std::to_string(sm.rows_per_env) + " / " +
+                std::to_string(m.rows_per_env) + "): another map");
+  if (memcmp(&sm.default_q, &m.default_q, 8) != 0) return fail("sfl_bank_copy: the source's default_q differs");
+  const double* q = nullptr;
+  const uint32_t* keys = nullptr;
+  if (kind == SFL_BANK_FROM_ENV) {
+    if (index >= src->E) return fail("sfl_bank_copy: env " + std::to_string(index) + " of " + std::to_string(src->E));
+    q = src->st.q + (size_t)index * m.q_per_env;
+    keys = src->st.touched + (size_t)index * m.touched_words;
+  } else if (kind == SFL_BANK_FROM_COHORT) {
+    if (index >= src->cons_n)
+      return fail("sfl_bank_copy: no consensus cohort " + std::to_string(index) + " (the source's last sfl_consensus made " +
+                  std::to_string(src->cons_n) + ")");
+    q = src->cons_q + (size_t)index * m.q_per_env;
+    keys = src->cons_keys + (size_t)index * m.touched_words;
+  } else {
+    return fail("sfl_bank_copy: kind " + std::to_string(kind) + " (SFL_BANK_FROM_ENV or SFL_BANK_FROM_COHORT)");
+  }
+  h->be.d2d(h->bank.q + (size_t)p * m.q_per_env, q, m.q_per_env * 8);
+  h->be.d2d(h->bank.keys + (size_t)p * m.touched_words, keys, (size_t)m.touched_words * 4);
+  if (h->be.sync()) return fail(std::string("sfl_bank_copy: ") + h->be.error());
+  h->bank.set[p] = 1;
+  return 0;
+}
+
+// one greedy episode per env from a reset (sfl_test's start and end: n_test 0, every env at PH_RESET before and
+// after), env e on table env_policy[e]; the fold behind the launch; the optional per-env outputs
+template <class B>
+int bank_eval(Handle<B>* h, const uint32_t* env_policy, sfl_eval_out* out) {
+  typename Handle<B>::Bank& bk = h->bank;
+  if (!bk.on) return fail("sfl_bank_eval: not an evaluation handle (sfl_create_eval)");
+  if (!env_policy) return fail("sfl_bank_eval: null env_policy");
+  const size_t E = h->E, T = h->map.T;
+  for (size_t e = 0; e < E; ++e) {
+    if (env_policy[e] >= bk.P)
+      return fail("sfl_bank_eval: env " + std::to_string(e) + " follows policy " + std::to_string(env_policy[e]) + " of " +
+                  std::to_string(bk.P));
+    if (!bk.set[env_policy[e]])
+      return fail("sfl_bank_eval: env " + std::to_string(e) + " follows policy " + std::to_string(env_policy[e]) +
+                  ", which was never set (sfl_bank_set / sfl_bank_copy)");
+  }
+  h->be.h2d(bk.policy, env_policy, E * 4);
+  if (int rc = test_begin(h)) return rc;  // (synchronises: env_policy is the caller's memory)
+  SflCtl c{};
+  c.mode = MODE_BANK;
+  c.ep_target = 1;
+  c.stats_cap = 1;
+  c.st_cum = bk.cum;
+  c.st_arrived = bk.arrived;
+  c.st_mf = bk.mf;
+  c.st_dec = bk.dec;
+  c.st_ticks = bk.ticks;
+  c.st_delays = bk.delays;
+  c.ev_at_dest = bk.at_dest;
+  c.ev_trunc = bk.trunc;
+  c.launch_dec = h->d_launch_dec;
+  c.launch_ticks = h->d_launch_ticks;
+  c.launch_bytes = h->d_launch_bytes;
+  float ms = 0.f;
+  bk.folded = false;
+  int rc = h->be.run(h->map, h->st, c, h->variant, &ms);
+  h->last_kernel_ms = ms;
+  EvalArgs a{};
+  a.E = h->E;
+  a.n_policies = bk.P;
+  a.T = h->map.T;
+  a.policy = bk.policy;
+  a.cum = bk.cum;
+  a.arrived = bk.arrived;
+  a.mf = bk.mf;
+  a.dec = bk.dec;
+  a.ticks = bk.ticks;
+  a.trunc = bk.trunc;
+  a.delays = bk.delays;
+  a.at_dest = bk.at_dest;
+  a.cells = bk.cells;
+  if (!rc) rc = h->be.eval_fold(a);  // (timed on its own: elapsed_ms after the sync below)
+  if (!rc && out) {
+    if (out->cum_reward) h->be.d2h_async(out->cum_reward, bk.cum, E * 8);
+    if (out->arrived) h->be.d2h_async(out->arrived, bk.arrived, E * 4);
+    if (out->malfunctions) h->be.d2h_async(out->malfunctions, bk.mf, E * 4);
+    if (out->decisions) h->be.d2h_async(out->decisions, bk.dec, E * 4);
+    if (out->ticks) h->be.d2h_async(out->ticks, bk.ticks, E * 4);
+    if (out->truncated) h->be.d2h_async(out->truncated, bk.trunc, E * 4);
+    if (out->delays) h->be.d2h_async(out->delays, bk.delays, T * E * 4);
+    if (out->at_dest) h->be.d2h_async(out->at_dest, bk.at_dest, T * E);
+  }
+  if (!rc) {  // leave the envs ready for a fresh episode, as sfl_test does
+    std::vector<int32_t> ph(E, PH_RESET);
+    h->be.h2d(h->st.phase, ph.data(), E * 4);
+    rc = h->be.sync();
+  }
+  if (rc) return fail(std::string("sfl_bank_eval: ") + h->be.error());
+  bk.last_ms = h->be.elapsed_ms();
+  bk.total_ms += bk.last_ms;
+  if (int rc2 = check_errors(h)) return rc2;
+  bk.folded = true;
+  return 0;
+}
+
+template <class B>
+int bank_read(Handle<B>* h, sfl_eval_cell* out) {
+  if (!h->bank.on) return fail("sfl_bank_read: not an evaluation handle (sfl_create_eval)");
+  if (!out) return fail("sfl_bank_read: null argument");
+  if (!h->bank.folded) return fail("sfl_bank_read: no successful sfl_bank_eval yet");
+  h->be.d2h(out, h->bank.cells, (size_t)h->bank.P * EV_WORDS * 8);
+  return h->be.sync() ? fail(h->be.error()) : 0;
+}
+
+// ---------------------------------------------------------------------------
 // external-action mode (include/sfl.h sfl_env_begin / sfl_env_step; SflExt in sfl_core.h)
 // ---------------------------------------------------------------------------
 // the row of external-action mode's wave kernel for a handle created on row v: v itself, but for the LM row its twin
@@ -879,6 +1083,7 @@ inline int ext_variant(int v) {
 template <class B>
 int env_begin(Handle<B>* h, bool wave = false) {
   const std::string fn = wave ? "sfl_env_begin_wave" : "sfl_env_begin";
+  if (h->bank.on) return fail(fn + ": an evaluation handle runs sfl_bank_eval only (sfl_create_eval)");
   if (h->part.world) return fail(fn + ": the handle is graph-partitioned");
   if (h->map.env_group) return fail(fn + ": the handle has hyperparameter groups (sfl_set_hparam_groups)");
   int variant = 0;
@@ -1068,6 +1273,7 @@ namespace sfl {
 template <class B>
 int part_config(Handle<B>* h, int rank, int world, const int32_t* owner, uint32_t env_base, uint32_t E_tot,
                 uint32_t cap_req, uint32_t cap_upd) {
+  if (h->bank.on) return fail("sfl_part_config: an evaluation handle has no per-env table to partition (sfl_create_eval)");
   if (world < 1 || rank < 0 || rank >= world || world > 255) return fail("sfl_part_config: bad rank / world");
   if (h->part.world) return fail("sfl_part_config: already configured");
   if (h->map.env_group) return fail("sfl_part_config: the handle has hyperparameter groups (sfl_set_hparam_groups)");
@@ -1381,6 +1587,7 @@ template <class B>
 int consensus(Handle<B>* h, int32_t mode, uint32_t flags, uint32_t n_cohorts, const uint32_t* env_cohort, double* kernel_ms) {
   if (mode != SFL_CONSENSUS_MEAN && mode != SFL_CONSENSUS_MAX)
     return fail("sfl_consensus: mode " + std::to_string(mode) + " (SFL_CONSENSUS_MEAN or SFL_CONSENSUS_MAX)");
+  if (h->bank.on) return fail("sfl_consensus: an evaluation handle has no per-env tables to merge (sfl_create_eval)");
   if (flags & ~(uint32_t)SFL_CONSENSUS_SHARE) return fail("sfl_consensus: unknown flag bits");
   if (h->part.world) return fail("sfl_consensus: the handle is graph-partitioned (its tables are owned rows)");
   if (h->env_mode) return fail("sfl_consensus: the handle is in external-action mode (no learner)");
@@ -1545,6 +1752,7 @@ int curve_end(Handle<B>* h) {
 template <class B>
 int curve_begin(Handle<B>* h, int32_t bin_episodes, int32_t n_bins, uint32_t n_series, const uint32_t* env_series,
                 int32_t ring_cap) {
+  if (h->bank.on) return fail("sfl_curve_begin: an evaluation handle has no sfl_step to fold (sfl_create_eval)");
   if (h->part.world) return fail("sfl_curve_begin: the handle is graph-partitioned (sfl_part_local records no episodes)");
   if (h->env_mode) return fail("sfl_curve_begin: the handle is in external-action mode (sfl_env_begin): no sfl_step to fold");
   if (bin_episodes < 1 || n_bins < 1 || n_series < 1 || ring_cap < 1)

@@ -100,6 +100,11 @@ struct HostBackend {
     return 0;
   }
   float elapsed_exploit_ms() { return 0.f; }
+  // sfl_bank_eval: the fold as a plain loop (sfl_eval.h)
+  int eval_fold(const sfl::EvalArgs& a) {
+    sfl::eval_fold_host(a);
+    return 0;
+  }
   int sync() { return 0; }
   uint64_t n_wait = 0;  // (nothing to wait for: the host build runs on the caller's thread)
   const uint32_t* seedseq_table() { return nullptr; }  // the host build draws every sub-generator

@@ -5,7 +5,8 @@
 // below -- variant 7 (the bench's c3 shape) in sfl_kwave_v7.hip with the register-minimising scheduler, the
 // HPG = true kernels (hyperparameter groups, sfl_set_hparam_groups: the plain launch of every shape) in
 // sfl_kwave_hpg.hip and -- variant 7 -- sfl_kwave_hpg_v7.hip, the EXT = true kernels (external-action mode,
-// sfl_env_begin_wave) in sfl_kwave_ext.hip, so that they compile in parallel with sfl.hip, which has all the others.
+// sfl_env_begin_wave) in sfl_kwave_ext.hip, the BANK = true kernels (policy-bank evaluation, sfl_bank_eval) in
+// sfl_kwave_bank.hip, so that they compile in parallel with sfl.hip, which has all the others.
 //
 // Waves per SIMD the grouped kernel is register-budgeted for (sfl::kVariants[v].OCC): shapes with one train
 // slot per lane (TW <= G) 4 -- c2 (variant 6): 918 M vs 805 M at 3 (VGPR-bound, spills a little; 5: 589 M) --,
@@ -52,21 +53,44 @@ k_wave_g(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict__ s,
   sfl::wave::run_groups<PPL, SPL, TW, TRACE, G, TIMED, LM, HPG, EXT>(*m, *s, *c);
 }
 
+// BANK: policy-bank evaluation (sfl_bank_eval; sfl_wave.h BANK): one greedy episode per env on a table of the handle's
+// read-only bank.  Kernels of their own names with the shape's arguments only (no trace, no timers, no groups), so the
+// existing kernels keep their symbols; the same launch bounds and register budgets as the shape's other kernels.
+template <int PPL, int SPL, int TW>
+__global__ void __launch_bounds__(SFL_WAVE_BLOCK) __attribute__((amdgpu_waves_per_eu(SFL_WAVE_OCC)))
+k_wave_bank(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict__ s, const sfl::SflCtl* __restrict__ c) {
+  sfl::wave::run<PPL, SPL, TW, false, false, false, false, false, true>(*m, *s, *c);
+}
+template <int PPL, int SPL, int TW>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SFL_WAVE2_OCC)))
+k_wave2_bank(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict__ s, const sfl::SflCtl* __restrict__ c) {
+  sfl::wave::run<PPL, SPL, TW, false, false, false, false, false, true>(*m, *s, *c);
+}
+template <int PPL, int SPL, int TW, int G, int OCC, bool LM>
+__global__ void __launch_bounds__(SFL_GROUP_BLOCK) __attribute__((amdgpu_waves_per_eu(OCC)))
+k_wave_g_bank(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict__ s, const sfl::SflCtl* __restrict__ c) {
+  sfl::wave::run_groups<PPL, SPL, TW, false, G, false, LM, false, false, true>(*m, *s, *c);
+}
+
 // ---- one launch path from the shape table ---------------------------------------------------------------------
 // A cell = a row v of sfl::kVariants (1 .. kNumVariants - 1) x a launch mode.  Everything about a cell follows from
 // the row: its kernel family, its grid and block, and the translation unit that compiles it.
 static_assert(sizeof(sfl::kVariants) / sizeof(sfl::kVariants[0]) == sfl::kNumVariants, "kNumVariants counts kVariants' rows");
 // Hpg: a handle with hyperparameter groups (plain only); Ext: a handle in external-action mode on the wave kernels
-// (sfl_env_begin_wave) -- every row but the LM one, whose handles step the same shape without the LDS tables
-enum class Mode { Plain, Trace, Timed, Hpg, Ext };
+// (sfl_env_begin_wave) -- every row but the LM one, whose handles step the same shape without the LDS tables;
+// Bank: an evaluation handle's episode launch (sfl_bank_eval) -- every row, the LM one with a cell of its own (a
+// launch is a whole episode, hundreds of decisions per env, which is what the copy of the tables into LDS pays for;
+// external-action mode's single decision per launch is not)
+enum class Mode { Plain, Trace, Timed, Hpg, Ext, Bank };
 // libsfl.so's translation units (build.TUS): sfl.hip, sfl_kwave_v7.hip, sfl_kwave_hpg.hip, sfl_kwave_hpg_v7.hip,
-// sfl_kwave_ext.hip
-enum class Unit { Main, V7, Hpg, HpgV7, Ext };
+// sfl_kwave_ext.hip, sfl_kwave_bank.hip
+enum class Unit { Main, V7, Hpg, HpgV7, Ext, Bank };
 constexpr int kSchedVariant = 7;  // the bench's c3 shape: its units are built with the register-minimising scheduler
 // the unit that owns a cell: it alone instantiates the cell's kernel, with its own compiler flags.  Every cell has
 // exactly one owner (this function's value); a unit that does not define its launch_unit fails the link.
 constexpr Unit owner(int v, Mode md) {
   if (md == Mode::Ext) return Unit::Ext;
+  if (md == Mode::Bank) return Unit::Bank;
   if (md == Mode::Hpg) return v == kSchedVariant ? Unit::HpgV7 : Unit::Hpg;
   return v == kSchedVariant ? Unit::V7 : Unit::Main;
 }
@@ -93,7 +117,14 @@ inline void launch_cell(const Launch& l) {
     constexpr sfl::WaveShape w = sfl::kVariants[V];
     constexpr bool TRACE = MD == Mode::Trace, TIMED = MD == Mode::Timed, HPG = MD == Mode::Hpg, EXT = MD == Mode::Ext;
     if (l.variant != V || l.mode != MD) return;
-    if constexpr (EXT && w.LM)
+    if constexpr (MD == Mode::Bank) {
+      if constexpr (w.G < 64)
+        k_wave_g_bank<w.PPL, w.SPL, w.TW, w.G, w.OCC, (bool)w.LM><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
+      else if constexpr (two_slot(w))
+        k_wave2_bank<w.PPL, w.SPL, w.TW><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
+      else
+        k_wave_bank<w.PPL, w.SPL, w.TW><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
+    } else if constexpr (EXT && w.LM)
       return;  // (no such cell: ext_variant maps the row to its twin)
     else if constexpr (w.G < 64)
       k_wave_g<w.PPL, w.SPL, w.TW, TRACE, w.G, w.OCC, TIMED, (bool)w.LM, HPG, EXT><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
@@ -106,7 +137,7 @@ inline void launch_cell(const Launch& l) {
 template <Unit U, int... I>
 inline void launch_owned(const Launch& l, std::integer_sequence<int, I...>) {
   ((launch_cell<U, I + 1, Mode::Plain>(l), launch_cell<U, I + 1, Mode::Trace>(l), launch_cell<U, I + 1, Mode::Timed>(l),
-    launch_cell<U, I + 1, Mode::Hpg>(l), launch_cell<U, I + 1, Mode::Ext>(l)), ...);
+    launch_cell<U, I + 1, Mode::Hpg>(l), launch_cell<U, I + 1, Mode::Ext>(l), launch_cell<U, I + 1, Mode::Bank>(l)), ...);
 }
 // a unit's launches: declared here, defined (SFL_KWAVE_UNIT) in the unit itself
 template <Unit U>
@@ -121,6 +152,8 @@ template <>
 void launch_unit<Unit::HpgV7>(const Launch& l);
 template <>
 void launch_unit<Unit::Ext>(const Launch& l);
+template <>
+void launch_unit<Unit::Bank>(const Launch& l);
 #define SFL_KWAVE_UNIT(U)                                                                           \
   template <>                                                                                       \
   void sflk::launch_unit<sflk::Unit::U>(const sflk::Launch& l) {                                    \
@@ -134,6 +167,7 @@ inline void launch(const Launch& l) {
     case Unit::Hpg: return launch_unit<Unit::Hpg>(l);
     case Unit::HpgV7: return launch_unit<Unit::HpgV7>(l);
     case Unit::Ext: return launch_unit<Unit::Ext>(l);
+    case Unit::Bank: return launch_unit<Unit::Bank>(l);
   }
 }
 

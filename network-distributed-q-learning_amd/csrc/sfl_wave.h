@@ -301,8 +301,16 @@ struct PortRec {
 // observed and emitted in one launch (decide() returns true, F_EXT_OBS) and applied in the next after observing it
 // again.  No learner: no Q-table, key set, epsilon / lr table, epsilon-greedy stream or interaction counters are
 // read or written; the staging holds the deciding train's record only, and only its slot word and distances
-template <int PPL, int SPL, int TWc, bool PART = false, int G = 64, bool LM = false, bool HPG = false, bool EXT = false>
+// BANK: policy-bank evaluation (sfl_bank_eval): one greedy episode per launch on a read-only table of
+// the handle's bank, SflMap::bank_q + bank_policy[e] * q_per_env, instead of the env's own.  Always greedy, so the
+// learner's half is compiled out: the epsilon draw and its LDS stream, the interaction counters, the pending-update
+// words and the Q update of post (a greedy post writes the successor slot's reward only), the arrival bonus, and every
+// key-set insert (the bank is never written).  The env's policy index is a group-uniform register (an SGPR at G = 64,
+// where the table's base pointer is held instead): see qbase()
+template <int PPL, int SPL, int TWc, bool PART = false, int G = 64, bool LM = false, bool HPG = false, bool EXT = false,
+          bool BANK = false>
 struct WEnv {
+  static_assert(!(BANK && (PART || HPG || EXT)), "policy-bank evaluation: the plain shapes (and the LM one) only");
   static_assert(!(HPG && PART), "hyperparameter groups are not part of the partitioned local step");
   static_assert(!(EXT && (PART || HPG || LM)), "external-action mode: the plain shapes only");
   static_assert(G == 64 || G == 32 || G == 16 || G == 8, "lane group of 8, 16, 32 or 64 lanes");
@@ -367,6 +375,7 @@ struct WEnv {
   bool pf_ok;        // uniform: this batch has been prefetched
   uint32_t lerr;  // error bits seen by this lane (OR-reduced on store)
   uint32_t hgrp = 0;  // HPG: the env's hyperparameter group (G = 64: wave-uniform, in an SGPR), loaded by load()
+  uint32_t pol = 0;   // BANK, G < 64: the bank table the env follows (group-uniform), loaded by load()
   // this env's blocks: Q-table, key-set bitmap, (switch, train) slots (env-major [T][S] here,
   // so one env's slots are contiguous and a flush over switches is one coalesced access)
   double* qb;
@@ -434,6 +443,9 @@ struct WEnv {
       touchb = P_->touched_own + ge * P_->own_words;
     } else if constexpr (EXT) {  // (no learner)
       qb = nullptr;
+      touchb = nullptr;
+    } else if constexpr (BANK) {  // (G = 64: the table's base, wave-uniform; G < 64: qbase() from `pol`)
+      qb = G == 64 ? const_cast<double*>(m.bank_q) + (size_t)U(ld(m.bank_policy, (size_t)e_)) * m.q_per_env : nullptr;
       touchb = nullptr;
     } else {
       qb = s.q + (size_t)e * m.q_per_env;
@@ -798,8 +810,13 @@ struct WEnv {
   // ---- Q-table ------------------------------------------------------------------------------
   // the env's global blocks; G < 64 recomputes them from e at each use (a held 64-bit pointer is
   // two VGPRs per block for the whole loop)
+  // BANK: the env's table of the bank.  Its index is loaded once (load()) and kept in one group-uniform VGPR at
+  // G < 64 -- half of a held pointer, and no LDS read in front of every Q address as a copy beside the env record
+  // would be (the staging's Q loads are the last level of a chain of dependent loads already); the registers the
+  // epsilon draw and the Q update no longer hold pay for it several times over (profiles/eval_bank_kres.txt)
   __device__ __forceinline__ double* qbase() const {
     if constexpr (PART || G == 64) return qb;
+    else if constexpr (BANK) return const_cast<double*>(m.bank_q) + (size_t)pol * m.q_per_env;
     else return s.q + (size_t)e * m.q_per_env;
   }
   __device__ __forceinline__ uint32_t* tbase() const {
@@ -813,6 +830,7 @@ struct WEnv {
   // global-address-space atomic: a flat atomic would also count on lgkmcnt, so the decision's next
   // LDS read or scalar load would wait for its L2 round trip
   __device__ __forceinline__ void touch_row(uint32_t row) const {
+    if constexpr (BANK) return;  // (the bank is read-only: a greedy run's key-set inserts are not recorded)
     __hip_atomic_fetch_or((SFL_AS_G uint32_t*)tbase() + (row >> 5), 1u << (row & 31u), __ATOMIC_RELAXED,
                           __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -890,7 +908,7 @@ struct WEnv {
 #pragma unroll
     for (int k = 0; k < PPL; ++k) rw[k] = ld(sem_words(), pix(k * G + lane < m.NP ? k * G + lane : 0));
 #pragma unroll
-    for (int k = 0; k < SPL; ++k) nw[k] = EXT ? 0u : ld(s.counts, cix(k * G + lane < m.S ? k * G + lane : 0));
+    for (int k = 0; k < SPL; ++k) nw[k] = (EXT || BANK) ? 0u : ld(s.counts, cix(k * G + lane < m.S ? k * G + lane : 0));
 #pragma unroll
     for (int k = 0; k < TPL; ++k) {
       const int hk = lane + G * k;
@@ -930,7 +948,7 @@ struct WEnv {
       if constexpr (PART) lsem0[k * G + lane] = r;
     }
 #pragma unroll
-    for (int k = 0; !EXT && k < SPL; ++k) {
+    for (int k = 0; !EXT && !BANK && k < SPL; ++k) {
       const uint32_t n = k * G + lane < m.S ? nw[k] : 0u;
       lcnt[k * G + lane] = n;
     }
@@ -972,6 +990,7 @@ struct WEnv {
       return;
     }
     if constexpr (HPG) hgrp = U((uint32_t)ld(m.env_group, (size_t)e));
+    if constexpr (BANK && G < 64) pol = U(ld(m.bank_policy, (size_t)e));
     now = U(ld(s.elapsed, e));
     flags = U(ld(s.eflags, e));
     epoch = U(ld(s.epoch, e));
@@ -988,7 +1007,7 @@ struct WEnv {
     arr_mask = mask(1);
     fl_mask = mask(2);
     mf_mask = mask(3);
-    if (!EXT && lane < 5) lrng[lane] = ld(s.rng, ix((size_t)lane));
+    if (!EXT && !BANK && lane < 5) lrng[lane] = ld(s.rng, ix((size_t)lane));
     cum = (int64_t)Ud(ld(s.cum_reward, e));
     n_mf = U(ld(s.n_mf, e));
     ep_dec = U(ld(s.ep_dec, e));
@@ -1042,7 +1061,7 @@ struct WEnv {
       if constexpr (PART) r0[k] = lsem0[k * G + lane];
     }
 #pragma unroll
-    for (int k = 0; !EXT && k < SPL; ++k) {
+    for (int k = 0; !EXT && !BANK && k < SPL; ++k) {
       nw[k] = lcnt[k * G + lane];
       if constexpr (PART) n0[k] = (ldirty[(k * G + lane) >> 5] >> ((k * G + lane) & 31)) & 1u;
     }
@@ -1054,7 +1073,7 @@ struct WEnv {
 #pragma unroll
     for (int k = 0; k < SPL; ++k) {
       const int sw = k * G + lane;
-      if (!EXT && sw < m.S && (!PART || n0[PART ? k : 0] != 0u)) st(s.counts, cix(sw), nw[k]);
+      if (!EXT && !BANK && sw < m.S && (!PART || n0[PART ? k : 0] != 0u)) st(s.counts, cix(sw), nw[k]);
     }
     uint32_t err = 0;
 #pragma unroll
@@ -1084,7 +1103,7 @@ struct WEnv {
       put(1, arr_mask);
       put(2, fl_mask);
       put(3, mf_mask);
-      if constexpr (!EXT) {
+      if constexpr (!EXT && !BANK) {
         st(s.rng, ix(0), lrng[0]);
         st(s.rng, ix(1), lrng[1]);
         st(s.rng, ix(4), lrng[4]);
@@ -1545,6 +1564,7 @@ struct WEnv {
   // Q values are dropped when the batch writes their cell (pf_written).  Slot words are never
   // stale: a decision writes only its own train's slots and a train decides once per batch.
   __device__ __forceinline__ void prefetch(bool greedy) {
+    if constexpr (BANK) greedy = true;
     PrioGuard<PART ? 0 : SFL_SETPRIO_PF> prio;
     const Mask malf = malf_kept();
 #pragma unroll
@@ -1603,6 +1623,7 @@ struct WEnv {
   __device__ __forceinline__ void prefetch_slot(const int hk, const int rec, const uint32_t sdec_k, const uint32_t nprv_k,
                                                 const uint32_t bits_k, const int32_t pos_k, const uint32_t plan_k, Mask malf,
                                                 bool greedy, uint32_t& roff_out, uint32_t& qoff_out) {
+    if constexpr (BANK) greedy = true;  // (no pending update is read: `hp` below is constant)
     if constexpr (xp::kNoPrefetch) {
       roff_out = qoff_out = PF_NONE;
       return;
@@ -1706,7 +1727,7 @@ struct WEnv {
       const double* rp = qbase() + (row_ok ? roff : 0u);
 #pragma unroll
       for (int c = 0; c < 4; ++c) rv[c] = ld(rp, (size_t)((uint32_t)c < w ? c : 0));
-      qv = ld(qbase(), (size_t)(hp ? qoff : 0u));
+      if constexpr (!BANK) qv = ld(qbase(), (size_t)(hp ? qoff : 0u));  // (BANK: no pending update, no cell to stage)
     }
     // the greedy choice on the staged row (distr_q.py:449-490, as in decide): valid whenever the
     // row is (a decision uses it only if its observation is the staged one)
@@ -1789,6 +1810,7 @@ struct WEnv {
   // observation is emitted again
   template <bool TM = false>
   __device__ __forceinline__ bool decide(Dec& d, bool greedy, int32_t x_act = -1, bool x_open = false) {
+    if constexpr (BANK) greedy = true;  // (the epsilon draw, its stream and the interaction count are dead code)
     PrioGuard<PART ? 0 : SFL_SETPRIO_DECIDE> prio;
     // PART: a row of this rank's own switches is decided in one pass, like the fused kernel
     const bool loc = local_sw((int)(trl(sdec, mctz(q_mask)) >> 16));
@@ -2174,7 +2196,7 @@ struct WEnv {
       post_part(d, greedy);
       return;
     }
-    if (greedy) {
+    if (BANK || greedy) {
       if (lid() == 0) {
         if (d.touch_cur) touch_row(d.row_cur);
         st(sbase(), slot_ix(d.next_sw, d.h), slot_make(PEND_NONE, d.r_new, epoch));
@@ -2406,6 +2428,29 @@ struct WEnv {
     if (c.launch_bytes) st(c.launch_bytes, e, (uint64_t)abytes);
   }
 
+  // BANK: the env's outputs at its episode's end (sfl_bank_eval's sfl_eval_out; the fold of sfl_eval.hip reads them):
+  // row 0 of the statistics buffers from the env's lane 0, each train's delay and, beside it, whether it stands at its
+  // destination (state DONE: the reference's trains_at_dest) from the lane that holds the train -- plain vector
+  // stores, every buffer [..][E]
+  __device__ __forceinline__ void bank_end(const SflCtl& c, int ln) {
+    if (ln == 0) {
+      st(c.st_cum, (size_t)e, (double)cum);
+      st(c.st_arrived, (size_t)e, (int32_t)mpopc(arr_mask));
+      st(c.st_mf, (size_t)e, n_mf);
+      st(c.st_dec, (size_t)e, ep_dec);
+      st(c.st_ticks, (size_t)e, ep_ticks);
+      st(c.ev_trunc, (size_t)e, (int32_t)((int64_t)ep_dec > m.max_steps ? 1 : 0));
+    }
+#pragma unroll
+    for (int k = 0; k < TPL; ++k) {
+      const int hk = ln + G * k;
+      if (mine[k]) {
+        st(c.st_delays, (size_t)hk * E + e, delay[k]);
+        st(c.ev_at_dest, (size_t)hk * E + e, (uint8_t)(tb_state(bits[k]) == S_DONE ? 1 : 0));
+      }
+    }
+  }
+
   // ---- external-action mode (EXT): env_run_ext of sfl_core.h, operation for operation, for both drivers -------
   // One launch = one call of sfl_env_step: the env applies the caller's action to the observation the last launch
   // emitted, runs on to its next observation (or its episode's end) and stops there.  A flat loop like
@@ -2560,10 +2605,14 @@ struct PhaseTimer {
 };
 
 // EXT: one call of external-action mode (WEnv::ext_run; c.ext = the call's SflExt)
-template <int PPL, int SPL, int TW, bool TRACE, bool PART = false, bool TIMED = false, bool HPG = false, bool EXT = false>
+// BANK: one greedy episode on the env's table of the policy bank (sfl_bank_eval): the launch starts at PH_RESET and
+// the env stops at its episode's end, where bank_end() writes its outputs
+template <int PPL, int SPL, int TW, bool TRACE, bool PART = false, bool TIMED = false, bool HPG = false, bool EXT = false,
+          bool BANK = false>
 __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const SflPart* P = nullptr) {
   static_assert(!(EXT && (TRACE || TIMED)), "external-action mode: no trace, no phase timers");
-  using V = WEnv<PPL, SPL, TW, PART, 64, false, HPG, EXT>;
+  static_assert(!(BANK && (TRACE || TIMED)), "policy-bank evaluation: no trace, no phase timers");
+  using V = WEnv<PPL, SPL, TW, PART, 64, false, HPG, EXT, BANK>;
   // semaphores, counters, prefetch records, rng, timetable (PART: one record, timetable from the map)
   // (PART: the launch's initial records / counters in place of the timetable copy)
   constexpr int LDS_WORDS =
@@ -2595,12 +2644,14 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
   int32_t n_test = PART ? (int32_t)v.ebw(EB_N_TEST) : uni(ld(s.n_test, e));
   uint32_t ticks = 0, abytes = 0;
   typename V::Dec d;
-  const bool test_mode = c.mode == 1;
-  const int64_t max_steps = m.max_steps, dec_budget = c.dec_budget;
+  const bool test_mode = BANK || c.mode == 1;
+  const int64_t max_steps = m.max_steps, dec_budget = BANK ? 0 : c.dec_budget;
   while (true) {
     if (phase == PH_RESET) {
       // learn: optional greedy round before episode t (distr_q.py:278-281)
-      if (test_mode) {
+      if constexpr (BANK) {
+        v.flags |= F_GREEDY;
+      } else if (test_mode) {
         if (c.ep_target >= 0 && n_test >= c.ep_target) break;
         v.flags |= F_GREEDY;
       } else {
@@ -2620,7 +2671,7 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
       ticks++;
       phase = v.after_tick();
     } else if (phase == PH_DECIDE || phase == PH_POST) {
-      const bool greedy = (v.flags & F_GREEDY) != 0;
+      const bool greedy = BANK || (v.flags & F_GREEDY) != 0;
       // post step + loop bookkeeping of decision d; true: the launch's decision budget is spent
       auto finish = [&]() -> bool {
         if constexpr (TIMED) tm.lap(TM_OTHER);
@@ -2664,6 +2715,12 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
       }
       if (stop) break;
     } else {  // PH_END
+      if constexpr (BANK) {  // the env's outputs; the launch is this one episode
+        v.bank_end(c, lane);
+        n_test += 1;
+        phase = PH_RESET;
+        break;
+      }
       const int arrived = mpopc(v.arr_mask);
       const size_t cap = (size_t)(c.stats_cap > 0 ? c.stats_cap : 1);
       const bool greedy = (v.flags & F_GREEDY) != 0;
@@ -2710,10 +2767,12 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
 // follow it -- as a flat loop in which each iteration advances every group by at most one tick,
 // one post step and one decision.  The groups of a wave diverge (one ticks while another decides);
 // a batch loop as in run() would hold every group until the longest batch of the wave is done.
-template <int PPL, int SPL, int TW, bool TRACE, int G, bool TIMED = false, bool LM = false, bool HPG = false, bool EXT = false>
+template <int PPL, int SPL, int TW, bool TRACE, int G, bool TIMED = false, bool LM = false, bool HPG = false, bool EXT = false,
+          bool BANK = false>
 __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) {
   static_assert(!(EXT && (TRACE || TIMED)), "external-action mode: no trace, no phase timers");
-  using V = WEnv<PPL, SPL, TW, false, G, LM, HPG, EXT>;
+  static_assert(!(BANK && (TRACE || TIMED)), "policy-bank evaluation: no trace, no phase timers");
+  using V = WEnv<PPL, SPL, TW, false, G, LM, HPG, EXT, BANK>;
   // per env: semaphores, counters, prefetch records, rng; per block: the timetable rows and the
   // per-switch / per-port map records (the groups of a wave read different switches' records: LDS
   // reads instead of vector loads)
@@ -2764,17 +2823,20 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
   int32_t ep_t = ld(s.ep_t, e), n_test = ld(s.n_test, e);
   uint32_t ticks = 0, abytes = 0;
   typename V::Dec d;
-  const bool test_mode = c.mode == 1;
+  const bool test_mode = BANK || c.mode == 1;
   // 32-bit bounds (step_ctr and n_dec are 32-bit counters): held as two 64-bit values across the
   // loop they were spilled, and the decision count reloaded from scratch every post (c3: 1,356 M ->
   // 1,404 M agent-env-steps/s)
   const int32_t max_steps = m.max_steps < 0x7FFFFFFF ? (int32_t)m.max_steps : 0x7FFFFFFF;
-  const uint32_t dec_budget = c.dec_budget > 0 ? (c.dec_budget < 0xFFFFFFFFll ? (uint32_t)c.dec_budget : 0xFFFFFFFFu) : 0xFFFFFFFFu;
+  const uint32_t dec_budget =
+      (!BANK && c.dec_budget > 0) ? (c.dec_budget < 0xFFFFFFFFll ? (uint32_t)c.dec_budget : 0xFFFFFFFFu) : 0xFFFFFFFFu;
   while (true) {
     if (phase == PH_RESET) {
       // learn: optional greedy round before episode t (distr_q.py:278-281)
       bool target = false;
-      if (test_mode) {
+      if constexpr (BANK) {
+        v.flags |= F_GREEDY;
+      } else if (test_mode) {
         target = c.ep_target >= 0 && n_test >= c.ep_target;
         v.flags |= F_GREEDY;
       } else {
@@ -2810,7 +2872,7 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
     }
     if constexpr (TIMED) tm.lap(TM_TICK);
     if (phase == PH_POST) {  // post step + loop bookkeeping of the decision in flight
-      const bool greedy = (v.flags & F_GREEDY) != 0;
+      const bool greedy = BANK || (v.flags & F_GREEDY) != 0;
       v.post(d, greedy);
       if (TRACE && c.trace && (int32_t)e == c.trace_env) v.trace_decision(c, d, v.lane);
       v.count_decision(d, max_steps);
@@ -2823,13 +2885,21 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
     }
     const uint64_t dec_lanes = TIMED ? (uint64_t)__ballot(phase == PH_DECIDE) : 0ull;
     if (phase == PH_DECIDE) {
-      const bool greedy = (v.flags & F_GREEDY) != 0;
+      const bool greedy = BANK || (v.flags & F_GREEDY) != 0;
       v.template decide<TIMED>(d, greedy);
       abytes += d.abytes;
       v.flags |= F_INFLIGHT;
       phase = many(v.q_mask) ? PH_POST : PH_TICK;
     }
     if constexpr (TIMED) tm.decide_done(v, dec_lanes ? __builtin_ctzll(dec_lanes) : -1);
+    if constexpr (BANK) {
+      if (phase == PH_END) {  // the env's outputs; the launch is this one episode (the group leaves the loop)
+        v.bank_end(c, v.lane);
+        n_test += 1;
+        phase = PH_RESET;
+        break;
+      }
+    }
     if (phase == PH_END) {
       const int arrived = mpopc(v.arr_mask);
       const size_t cap = (size_t)(c.stats_cap > 0 ? c.stats_cap : 1);

@@ -57,6 +57,102 @@ def raw_to_dict(cm: CompiledMap, default_q: float, q: np.ndarray, touched: np.nd
     return out
 
 
+def dict_to_raw(cm: CompiledMap, default_q: float, table: Dict[tuple, list]) -> Tuple[np.ndarray, np.ndarray]:
+    """Inverse of ``raw_to_dict`` (``DistrQLearning.load``): the reference's ``q_table`` dict as a compact Q block and
+    key-set bitmap; rejects rows the compact layout cannot hold."""
+    A = cm.arrays
+    dq = float(default_q)
+    q = np.full(cm.q_per_env, dq)
+    touched = np.zeros((cm.rows_per_env + 31) // 32, np.uint32)
+    sidx = {sid: i for i, sid in enumerate(cm.switch_ids)}
+    kidx = {st: i for i, st in enumerate(cm.stations)}
+    for key, vals in table.items():
+        s = sidx[(int(key[0]), int(key[1]))]
+        P_ = len(cm.ports[s])
+        sem = key[2:2 + P_]
+        tgt = key[2 + P_:2 + 3 * P_]
+        dl = key[2 + 3 * P_:2 + 4 * P_]
+        slots = [i for i in range(P_) if dl[i] != -1]
+        if len(slots) != 1:
+            raise ValueError(f"row {key} has no unique in-port")
+        slot = slots[0]
+        k = kidx[(int(tgt[2 * slot]), int(tgt[2 * slot + 1]))]
+        bits = sum(int(b) << j for j, b in enumerate(sem))
+        stt = (bits * cm.K + k) * 3 + int(dl[slot])
+        g = 4 * s + slot
+        w, off = int(A["q_w"][g]), int(A["q_off"][g])
+        routes = [a for a, (src, _) in enumerate(cm.outcomes[s]) if src == slot] + [int(cm.n_actions[s]) - 1]
+        for a, v in enumerate(vals):
+            if a not in routes and float(v) != dq:
+                raise ValueError(f"row {key}: action {a} does not leave from the in-port; not representable")
+        for j, a in enumerate(routes):
+            q[off + stt * w + j] = float(vals[a])
+        rid = int(A["row_base"][g]) + stt
+        touched[rid >> 5] |= np.uint32(1 << (rid & 31))
+    return q, touched
+
+
+def _descriptors(cm: CompiledMap, hp: dict, max_steps: int, ntab: int, delay_threshold: int):
+    """The sfl_map_desc and sfl_hparams of a handle on ``cm`` (Batch and EvalBatch): (map descriptor, hyperparameters,
+    the arrays they point at -- to be kept alive until the create call has copied them)."""
+    A = cm.arrays
+    sc = cm.scenario
+    keep = []
+
+    def arr(name, dtype):
+        a = np.ascontiguousarray(A[name], dtype=dtype)
+        keep.append(a)
+        return a
+
+    md = _lib.MapDesc()
+    md.H, md.W, md.S, md.T, md.K = cm.H, cm.W, cm.S, cm.T, cm.K
+    md.max_episode_steps = sc.max_episode_steps
+    md.mf_rate, md.mf_min, md.mf_max = sc.malfunction_rate, sc.malfunction_min, sc.malfunction_max
+    md.q_per_env, md.rows_per_env = cm.q_per_env, cm.rows_per_env
+    md.delay_threshold = int(delay_threshold)
+    spec = [("grid", np.uint16, C.c_uint16), ("cell_sw", np.int16, C.c_int16), ("sw_np", np.uint8, C.c_uint8),
+            ("sw_na", np.uint8, C.c_uint8), ("act_src", np.uint8, C.c_uint8), ("act_dst", np.uint8, C.c_uint8),
+            ("act_turn", np.uint8, C.c_uint8), ("act_j", np.uint8, C.c_uint8),
+            ("first_other", np.uint8, C.c_uint8), ("port_side", np.uint8, C.c_uint8),
+            ("slot_nroutes", np.uint8, C.c_uint8), ("slot_route_act", np.uint8, C.c_uint8),
+            ("q_w", np.uint8, C.c_uint8), ("port_nb", np.int16, C.c_int16), ("port_len", np.int16, C.c_int16),
+            ("port_unique", np.int16, C.c_int16), ("q_off", np.uint64, C.c_uint64),
+            ("row_base", np.uint32, C.c_uint32), ("dist", np.int32, C.c_int32),
+            ("tr_ed", np.int32, C.c_int32), ("tr_la", np.int32, C.c_int32), ("tr_k", np.int32, C.c_int32),
+            ("tr_target", np.int32, C.c_int32), ("tr_init_cell", np.int32, C.c_int32),
+            ("tr_init_dist", np.int32, C.c_int32), ("tr_init_delay", np.int32, C.c_int32),
+            ("tr_init_dir", np.uint8, C.c_uint8), ("tr_init_port", np.int16, C.c_int16)]
+    for name, dt, ct in spec:
+        setattr(md, name, _ptr(arr(name, dt), ct))
+    eps_tab = eps_table(hp["epsilon"], hp["epsilon_decay_rate"], ntab)
+    lr_tab = lr_table(hp["lr"], hp["lr_decay_rate"], ntab)
+    h = _lib.HParams()
+    h.gamma, h.epsilon, h.epsilon_decay_rate = hp["gamma"], hp["epsilon"], hp["epsilon_decay_rate"]
+    h.lr, h.lr_decay_rate, h.default_q = hp["lr"], hp["lr_decay_rate"], hp["default_q"]
+    h.max_steps, h.ntab = int(max_steps), int(ntab)
+    h.eps_tab, h.lr_tab = _ptr(eps_tab, C.c_double), _ptr(lr_tab, C.c_double)
+    keep += [eps_tab, lr_tab]
+    return md, h, keep
+
+
+def _kernel_note(obj) -> str:
+    """The handle's kernel note (why it runs the lane-per-env body, "" on a wave kernel): warns, or with
+    SFL_REQUIRE_WAVE=1 closes ``obj`` and raises."""
+    note = C.create_string_buffer(256)
+    obj.lib.check(obj.lib.dll.sfl_get_kernel_note(obj.h, note, 256), "sfl_get_kernel_note")
+    text = note.value.decode()
+    if text:
+        # the lane-per-env body is 15-45x slower than k_wave: say so, or refuse when asked to
+        import os
+        import warnings
+        msg = f"this map runs the lane-per-env kernel (k_run), not k_wave: {text}"
+        if os.environ.get("SFL_REQUIRE_WAVE") == "1":
+            obj.close()
+            raise _lib.SflError(msg)
+        warnings.warn(msg, RuntimeWarning, stacklevel=3)
+    return text
+
+
 class Batch:
     """Owns one device handle.  ``hp`` uses the reference's DistrQLearning argument names."""
 
@@ -76,60 +172,16 @@ class Batch:
         self.seeds = [int(s) for s in seeds]
         self.E = len(self.seeds)
         self.lib = lib or _lib.load_product()
-        A = cm.arrays
         sc = cm.scenario
-        self._keep = []  # arrays referenced by the descriptor until sfl_create copies them
-
-        def arr(name, dtype):
-            a = np.ascontiguousarray(A[name], dtype=dtype)
-            self._keep.append(a)
-            return a
-
-        md = _lib.MapDesc()
-        md.H, md.W, md.S, md.T, md.K = cm.H, cm.W, cm.S, cm.T, cm.K
-        md.max_episode_steps = sc.max_episode_steps
-        md.mf_rate, md.mf_min, md.mf_max = sc.malfunction_rate, sc.malfunction_min, sc.malfunction_max
-        md.q_per_env, md.rows_per_env = cm.q_per_env, cm.rows_per_env
-        md.delay_threshold = int(delay_threshold)
-        spec = [("grid", np.uint16, C.c_uint16), ("cell_sw", np.int16, C.c_int16), ("sw_np", np.uint8, C.c_uint8),
-                ("sw_na", np.uint8, C.c_uint8), ("act_src", np.uint8, C.c_uint8), ("act_dst", np.uint8, C.c_uint8),
-                ("act_turn", np.uint8, C.c_uint8), ("act_j", np.uint8, C.c_uint8),
-                ("first_other", np.uint8, C.c_uint8), ("port_side", np.uint8, C.c_uint8),
-                ("slot_nroutes", np.uint8, C.c_uint8), ("slot_route_act", np.uint8, C.c_uint8),
-                ("q_w", np.uint8, C.c_uint8), ("port_nb", np.int16, C.c_int16), ("port_len", np.int16, C.c_int16),
-                ("port_unique", np.int16, C.c_int16), ("q_off", np.uint64, C.c_uint64),
-                ("row_base", np.uint32, C.c_uint32), ("dist", np.int32, C.c_int32),
-                ("tr_ed", np.int32, C.c_int32), ("tr_la", np.int32, C.c_int32), ("tr_k", np.int32, C.c_int32),
-                ("tr_target", np.int32, C.c_int32), ("tr_init_cell", np.int32, C.c_int32),
-                ("tr_init_dist", np.int32, C.c_int32), ("tr_init_delay", np.int32, C.c_int32),
-                ("tr_init_dir", np.uint8, C.c_uint8), ("tr_init_port", np.int16, C.c_int16)]
-        for name, dt, ct in spec:
-            setattr(md, name, _ptr(arr(name, dt), ct))
-        self.eps_tab = eps_table(hp["epsilon"], hp["epsilon_decay_rate"], ntab)
-        self.lr_tab = lr_table(hp["lr"], hp["lr_decay_rate"], ntab)
-        h = _lib.HParams()
-        h.gamma, h.epsilon, h.epsilon_decay_rate = hp["gamma"], hp["epsilon"], hp["epsilon_decay_rate"]
-        h.lr, h.lr_decay_rate, h.default_q = hp["lr"], hp["lr_decay_rate"], hp["default_q"]
-        h.max_steps, h.ntab = int(max_steps), int(ntab)
-        h.eps_tab, h.lr_tab = _ptr(self.eps_tab, C.c_double), _ptr(self.lr_tab, C.c_double)
+        md, h, keep = _descriptors(cm, hp, max_steps, ntab, delay_threshold)  # (alive until sfl_create has copied them)
+        self.eps_tab, self.lr_tab = keep[-2], keep[-1]
         seeds_a = np.array(self.seeds, dtype=np.uint64)
         handle = C.c_void_p()
         self.lib.check(self.lib.dll.sfl_create(C.byref(md), C.byref(h), self.E, _ptr(seeds_a, C.c_uint64), device,
                                                C.byref(handle)), "sfl_create")
         self.h = handle
-        self._keep = []
-        note = C.create_string_buffer(256)
-        self.lib.check(self.lib.dll.sfl_get_kernel_note(self.h, note, 256), "sfl_get_kernel_note")
-        self.kernel_note = note.value.decode()
-        if self.kernel_note:
-            # the lane-per-env body is 15-45x slower than k_wave: say so, or refuse when asked to
-            import os
-            import warnings
-            msg = f"this map runs the lane-per-env kernel (k_run), not k_wave: {self.kernel_note}"
-            if os.environ.get("SFL_REQUIRE_WAVE") == "1":
-                self.close()
-                raise _lib.SflError(msg)
-            warnings.warn(msg, RuntimeWarning, stacklevel=2)
+        del md, h, keep
+        self.kernel_note = _kernel_note(self)
         if self.malfunction_stream == "flatland":
             tab = mfstream.schedule(self.lib, sc, self.seeds)
             self.lib.check(self.lib.dll.sfl_set_mf_schedule(self.h, tab.shape[1], _ptr(tab, C.c_uint8)),
@@ -536,35 +588,148 @@ class Batch:
 
     def load_q_dict(self, env: int, table: Dict[tuple, list]):
         """Inverse of ``q_dict`` (``DistrQLearning.load``); rejects rows the compact layout cannot hold."""
-        cm = self.cm
-        A = cm.arrays
-        dq = float(self.hp["default_q"])
-        q = np.full(cm.q_per_env, dq)
-        touched = np.zeros((cm.rows_per_env + 31) // 32, np.uint32)
-        sidx = {sid: i for i, sid in enumerate(cm.switch_ids)}
-        kidx = {st: i for i, st in enumerate(cm.stations)}
-        for key, vals in table.items():
-            s = sidx[(int(key[0]), int(key[1]))]
-            P_ = len(cm.ports[s])
-            sem = key[2:2 + P_]
-            tgt = key[2 + P_:2 + 3 * P_]
-            dl = key[2 + 3 * P_:2 + 4 * P_]
-            slots = [i for i in range(P_) if dl[i] != -1]
-            if len(slots) != 1:
-                raise ValueError(f"row {key} has no unique in-port")
-            slot = slots[0]
-            k = kidx[(int(tgt[2 * slot]), int(tgt[2 * slot + 1]))]
-            bits = sum(int(b) << j for j, b in enumerate(sem))
-            stt = (bits * cm.K + k) * 3 + int(dl[slot])
-            g = 4 * s + slot
-            w, off = int(A["q_w"][g]), int(A["q_off"][g])
-            routes = [a for a, (src, _) in enumerate(cm.outcomes[s]) if src == slot] + [int(cm.n_actions[s]) - 1]
-            for a, v in enumerate(vals):
-                if a not in routes and float(v) != dq:
-                    raise ValueError(f"row {key}: action {a} does not leave from the in-port; not representable")
-            for j, a in enumerate(routes):
-                q[off + stt * w + j] = float(vals[a])
-            rid = int(A["row_base"][g]) + stt
-            touched[rid >> 5] |= np.uint32(1 << (rid & 31))
+        q, touched = dict_to_raw(self.cm, self.hp["default_q"], table)
         self.lib.check(self.lib.dll.sfl_set_q(self.h, env, _ptr(q, C.c_double), _ptr(touched, C.c_uint32)),
                        "sfl_set_q")
+
+
+class EvalBatch:
+    """A read-only bank of ``n_policies`` Q-tables and E envs that each run one greedy episode (``DistrQLearning.test``,
+    distr_q.py:184-241) on the table they follow, on their own seed: one evaluation handle (include/sfl.h
+    sfl_create_eval).  No env has a table of its own, so scoring a table on thousands of malfunction seeds costs the
+    env state only.  The bank is never written: the key-set rows the reference's ``test()`` adds while it looks rows up
+    are not recorded (the greedy choices, and every output, are the same)."""
+
+    def __init__(self, cm: CompiledMap, hp: dict, seeds: Sequence[int], n_policies: int,
+                 lib: Optional[_lib.Lib] = None, device: int = 0, max_steps: int = 100_000,
+                 malfunction_stream: str = "counter", delay_threshold: int = 20):
+        self.cm = cm
+        self.malfunction_stream = mfstream.check_stream(malfunction_stream)
+        self.hp = dict(hp)
+        self.seeds = [int(s) for s in seeds]
+        self.E = len(self.seeds)
+        self.P = int(n_policies)
+        self.lib = lib or _lib.load_product()
+        if self.P < 0 or self.P > 0xFFFFFFFF:
+            raise ValueError("EvalBatch: n_policies out of range")
+        md, h, keep = _descriptors(cm, hp, max_steps, 1, delay_threshold)  # (a greedy run reads no schedule table)
+        seeds_a = np.array(self.seeds, dtype=np.uint64)
+        handle = C.c_void_p()
+        self.lib.check(self.lib.dll.sfl_create_eval(C.byref(md), C.byref(h), self.E, _ptr(seeds_a, C.c_uint64), device,
+                                                    self.P, C.byref(handle)), "sfl_create_eval")
+        self.h = handle
+        del md, h, keep
+        self.kernel_note = _kernel_note(self)
+        if self.malfunction_stream == "flatland":
+            tab = mfstream.schedule(self.lib, cm.scenario, self.seeds)
+            self.lib.check(self.lib.dll.sfl_set_mf_schedule(self.h, tab.shape[1], _ptr(tab, C.c_uint8)),
+                           "sfl_set_mf_schedule")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.dll.sfl_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    counters = Batch.counters
+
+    # ---- the bank's tables ----
+    def set_policy_raw(self, p: int, q: np.ndarray, touched: np.ndarray) -> None:
+        """Fill table ``p`` from a compact Q block and key-set bitmap (the layout of ``Batch.q_raw``)."""
+        q = np.ascontiguousarray(q, np.float64)
+        touched = np.ascontiguousarray(touched, np.uint32)
+        if q.size != self.cm.q_per_env or touched.size != (self.cm.rows_per_env + 31) // 32:
+            raise ValueError("set_policy_raw: arrays do not match the map's Q layout")
+        self.lib.check(self.lib.dll.sfl_bank_set(self.h, int(p), _ptr(q, C.c_double), _ptr(touched, C.c_uint32)),
+                       "sfl_bank_set")
+
+    def policy_raw(self, p: int) -> Tuple[np.ndarray, np.ndarray]:
+        q = np.zeros(self.cm.q_per_env)
+        t = np.zeros((self.cm.rows_per_env + 31) // 32, np.uint32)
+        self.lib.check(self.lib.dll.sfl_bank_get(self.h, int(p), _ptr(q, C.c_double), _ptr(t, C.c_uint32)), "sfl_bank_get")
+        return q, t
+
+    def load_policy_dict(self, p: int, table: Dict[tuple, list]) -> None:
+        """Table ``p`` from the reference's ``q_table`` dict (``DistrQLearning.load``), as ``Batch.load_q_dict``."""
+        self.set_policy_raw(p, *dict_to_raw(self.cm, self.hp["default_q"], table))
+
+    def policy_dict(self, p: int) -> Dict[tuple, list]:
+        return raw_to_dict(self.cm, self.hp["default_q"], *self.policy_raw(p))
+
+    def copy_policy(self, p: int, batch: Batch, env: Optional[int] = None, cohort: Optional[int] = None) -> None:
+        """Table ``p`` from a training ``Batch`` on the same device, device to device: env ``env``'s table, or the
+        consensus table of cohort ``cohort`` of its last ``consensus`` call (exactly one of the two)."""
+        if (env is None) == (cohort is None):
+            raise ValueError("copy_policy: give exactly one of env and cohort")
+        kind, index = (_lib.BANK_FROM_ENV, env) if cohort is None else (_lib.BANK_FROM_COHORT, cohort)
+        if int(index) < 0:
+            raise ValueError("copy_policy: a negative index")
+        self.lib.check(self.lib.dll.sfl_bank_copy(self.h, int(p), batch.h, kind, int(index)), "sfl_bank_copy")
+
+    # ---- one greedy episode per env ----
+    def evaluate(self, env_policy: Optional[Sequence[int]] = None, per_env: bool = True) -> Dict[str, object]:
+        """Every env runs one greedy episode from a reset on table ``env_policy[e]`` (default ``e % n_policies``).
+        Returns ``policy`` [E]; with ``per_env`` the arrays ``cum_reward``, ``arrived``, ``num_malfunctions``,
+        ``decisions``, ``ticks``, ``truncated`` [E] and ``delays``, ``at_dest`` [T][E]; and ``table``: the int64 fields
+        of sfl_eval_cell (``_lib.EVAL_FIELDS``) as [P] arrays, reduced on the device, plus the means ``early_mean``,
+        ``late_mean``, ``not_arrived_mean`` (trains per episode), ``reward_mean``, ``decisions_per_episode``,
+        ``ticks_per_decision``, ``truncated_frac`` and ``all_arrived_frac`` -- NaN where a policy has no episode."""
+        E, T = self.E, self.cm.T
+        if env_policy is None:
+            pol = (np.arange(E, dtype=np.int64) % max(self.P, 1)).astype(np.uint32)
+        else:
+            if len(env_policy) != E:
+                raise ValueError(f"evaluate: env_policy must name a policy for each of the {E} envs")
+            ids = np.asarray(env_policy, dtype=np.int64)
+            if ids.min() < 0 or ids.max() > 0xFFFFFFFF:
+                raise ValueError("evaluate: policy ids must be non-negative")
+            pol = ids.astype(np.uint32)
+        out: Dict[str, object] = {}
+        o = _lib.EvalOut()
+        if per_env:
+            out = dict(cum_reward=np.zeros(E), arrived=np.zeros(E, np.int32), num_malfunctions=np.zeros(E, np.int32),
+                       decisions=np.zeros(E, np.int32), ticks=np.zeros(E, np.int32), truncated=np.zeros(E, np.int32),
+                       delays=np.zeros((T, E), np.int32), at_dest=np.zeros((T, E), np.uint8))
+            o.cum_reward = _ptr(out["cum_reward"], C.c_double)
+            o.arrived = _ptr(out["arrived"], C.c_int32)
+            o.malfunctions = _ptr(out["num_malfunctions"], C.c_int32)
+            o.decisions = _ptr(out["decisions"], C.c_int32)
+            o.ticks = _ptr(out["ticks"], C.c_int32)
+            o.truncated = _ptr(out["truncated"], C.c_int32)
+            o.delays = _ptr(out["delays"], C.c_int32)
+            o.at_dest = _ptr(out["at_dest"], C.c_uint8)
+        self.lib.check(self.lib.dll.sfl_bank_eval(self.h, _ptr(pol, C.c_uint32), C.byref(o)), "sfl_bank_eval")
+        cells = np.zeros((self.P, len(_lib.EVAL_FIELDS)), np.int64)
+        self.lib.check(self.lib.dll.sfl_bank_read(self.h, _ptr(cells, C.c_int64)), "sfl_bank_read")
+        out["policy"] = pol
+        out["table"] = eval_table(cells)
+        return out
+
+    def fold_ms(self) -> Tuple[float, float]:
+        """Device ms of the last fold and of all folds of this handle (never part of ``counters()['last_kernel_ms']``)."""
+        last, total = C.c_double(0.0), C.c_double(0.0)
+        self.lib.check(self.lib.dll.sfl_bank_fold_ms(self.h, C.byref(last), C.byref(total)), "sfl_bank_fold_ms")
+        return float(last.value), float(total.value)
+
+
+def eval_table(cells: np.ndarray) -> Dict[str, np.ndarray]:
+    """sfl_eval_cell words [P][15] as one [P] int64 array per field plus the per-episode means (NaN without episodes)."""
+    t = {k: np.ascontiguousarray(cells[:, i]) for i, k in enumerate(_lib.EVAL_FIELDS)}
+    n = t["episodes"].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        per_ep = lambda k: np.where(n > 0, t[k] / n, np.nan)  # noqa: E731
+        t["early_mean"] = per_ep("trains_early")
+        t["late_mean"] = per_ep("trains_late")
+        t["not_arrived_mean"] = per_ep("trains_not_arrived")
+        t["reward_mean"] = per_ep("reward_sum")
+        t["decisions_per_episode"] = per_ep("decisions_sum")
+        t["truncated_frac"] = per_ep("truncated")
+        t["all_arrived_frac"] = per_ep("all_arrived")
+        t["ticks_per_decision"] = np.where((n > 0) & (t["decisions_sum"] > 0),
+                                           t["ticks_sum"] / t["decisions_sum"].astype(np.float64), np.nan)
+    return t

@@ -2,7 +2,9 @@
 k_wave / k_wave2 / k_wave_g / k_wave_part / k_wave2_part instantiation, matched by shape (template arguments).  A
 trailing HPG = false argument (the hyperparameter-group switch, csrc/sfl_kwave_g.h) is dropped, so a library with it
 compares against one from before it; HPG = true kernels are listed on their own.  Likewise the EXT argument behind it
-(external-action mode's kernels, sfl_env_begin_wave).  The "code" column says whether the
+(external-action mode's kernels, sfl_env_begin_wave).  The policy-bank evaluation's kernels (k_wave_bank, k_wave2_bank,
+k_wave_g_bank: sfl_bank_eval) are listed as "BANK " + the key of their Plain twin, and a second table puts each beside
+that twin.  The "code" column says whether the
 kernel's machine code (the symbol's bytes in its code object's .text) is the same in both, or the same but for
 pc-relative addresses (same_code).  Exit status 1 if a kernel
 present in both differs in a resource field (registers, spills, scratch, LDS); code bytes alone do not fail.
@@ -61,10 +63,15 @@ def kernels_of(co):
     for blk in notes.split("- .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", blk).group(1)
         # (Itanium mangling: k_waveILi8ELi2ELb1E...E -- integer and bool template arguments only)
-        m = re.search(r"\d+(k_wave_g|k_wave2_part|k_wave_part|k_wave2|k_wave)I((?:L[ib]\d+E)+)E", name)
+        m = re.search(r"\d+(k_wave_g_bank|k_wave2_bank|k_wave_bank|k_wave_g|k_wave2_part|k_wave_part|k_wave2|k_wave)I((?:L[ib]\d+E)+)E", name)
         if not m:
             continue
         args = [("true" if v == "1" else "false") if t == "b" else v for t, v in re.findall(r"L([ib])(\d+)E", m.group(2))]
+        vals = [int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in FIELDS]
+        if m.group(1).endswith("_bank"):  # <PPL,SPL,TW[,G,OCC,LM]>: the key of the Plain twin (TRACE, TIMED false)
+            twin = args[:3] + ["false"] + (args[3:5] + ["false", args[5]] if len(args) == 6 else ["false"])
+            out["BANK " + m.group(1)[:-5] + "<" + ",".join(twin) + ">"] = vals + [size.get(name, -1), code.get(name)]
+            continue
         full = {"k_wave": 6, "k_wave2": 6, "k_wave_g": 9}.get(m.group(1))  # (the part kernels have no HPG argument)
         # (a trailing EXT argument behind HPG: external-action mode's kernels, listed on their own like HPG's)
         ext = full is not None and len(args) == full + 1 and args[-1] == "true"
@@ -74,7 +81,6 @@ def kernels_of(co):
         if len(args) == full:
             args = args[:-1]
         key = ("EXT " if ext else "") + ("HPG " if hpg else "") + m.group(1) + "<" + ",".join(args) + ">"
-        vals = [int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in FIELDS]
         out[key] = vals + [size.get(name, -1), code.get(name)]
     return out
 
@@ -119,6 +125,18 @@ def main(old, new, md=False):
     else:
         for r in [head] + rows:
             print(f"{r[0]:64s}" + "".join(f"{x:>24s}" for x in r[1:]))
+    banks = [k for k in sorted(b) if k.startswith("BANK ") and k[5:] in b]
+    if banks:
+        print("\npolicy-bank kernels of the new library beside their Plain twins (twin -> bank)")
+        bh = ["kernel"] + head[1:8]
+        brows = [[k[5:]] + [f"{x} -> {y}" for x, y in zip(b[k[5:]][:-1], b[k][:-1])] for k in banks]
+        if md:
+            print("| " + " | ".join(bh) + " |\n|" + "---|" * len(bh))
+            for r in brows:
+                print("| " + " | ".join(r) + " |")
+        else:
+            for r in [bh] + brows:
+                print(f"{r[0]:64s}" + "".join(f"{x:>24s}" for x in r[1:]))
     print(f"{sum(1 for k in a if k in b)} kernels in both, {len(set(a) ^ set(b))} in one only, {bad} differ in resources, "
           f"{recoded} in machine code")
     return 1 if bad else 0
