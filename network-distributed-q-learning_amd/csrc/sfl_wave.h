@@ -338,6 +338,10 @@ struct WEnv {
   // dependent loads instead of one per train slot; otherwise train h's lane stages it (slot h / G)
   static constexpr bool PF_BY_RANK = RING;
   static constexpr int PFS = PF_BY_RANK ? (PF_SLOTS + G - 1) / G : TPL;
+  // prefetch_slot's Q loads issued together, pending cell first, and held in front of the reduction by a scheduling
+  // barrier.  Not in the 16-switch grouped shapes of handles with hyperparameter groups: there the new order alone
+  // raised the scratch from 48 to 64 bytes per lane (scripts/kres_diff.py against the parent), so they keep the old one
+  static constexpr bool PF_PIN = !(HPG && PPL == 8 && G < 64);
   int pf_n = 0;  // RING: decisions since the batch was staged (= the record of the next one)
   static constexpr int kG = G;
   static_assert(TPL * G <= 128, "at most 128 train slots per env");
@@ -1721,13 +1725,20 @@ struct WEnv {
     const uint32_t qoff = pp[3] + ((pend >> 14) & 0x3FFFu) * (pp[1] >> 16) + ((pend >> 28) & 3u);
     // level 3: Q values
     // (PART: the rows live on their owners; nothing is staged.  EXT: there are none)
+    // (PF_PIN: all five loads in front of the first use of any.  The pending cell goes first -- another row of the
+    // block, the likeliest miss, and only the LDS store at the end needs it -- then the row's columns, clamped to the
+    // row's width.  The scheduling barrier holds the reduction behind them: left alone, the register-minimising
+    // scheduler of variant 7's unit sinks each column's load to its compare and the cell's to its store, five round
+    // trips one after the other)
     double rv[4] = {0.0, 0.0, 0.0, 0.0};
     double qv = 0.0;
     if constexpr (!PART && !EXT) {
+      if constexpr (!BANK && PF_PIN) qv = ld(qbase(), (size_t)(hp ? qoff : 0u));  // (BANK: no pending update, no cell to stage)
       const double* rp = qbase() + (row_ok ? roff : 0u);
 #pragma unroll
       for (int c = 0; c < 4; ++c) rv[c] = ld(rp, (size_t)((uint32_t)c < w ? c : 0));
-      if constexpr (!BANK) qv = ld(qbase(), (size_t)(hp ? qoff : 0u));  // (BANK: no pending update, no cell to stage)
+      if constexpr (!BANK && !PF_PIN) qv = ld(qbase(), (size_t)(hp ? qoff : 0u));
+      if constexpr (PF_PIN) __builtin_amdgcn_sched_barrier(0);
     }
     // the greedy choice on the staged row (distr_q.py:449-490, as in decide): valid whenever the
     // row is (a decision uses it only if its observation is the staged one)
