@@ -557,6 +557,59 @@ int sfl_bank_copy(sfl_handle* h, uint32_t p, sfl_handle* src, int32_t kind, uint
 int sfl_bank_eval(sfl_handle* h, const uint32_t* env_policy /* [n_envs] */, sfl_eval_out* out /* may be NULL */);
 int sfl_bank_read(sfl_handle* h, sfl_eval_cell* out /* [n_policies] */);
 int sfl_bank_fold_ms(sfl_handle* h, double* last_ms, double* total_ms /* either may be NULL */);
+
+/* ---- suspend and resume: a batch's state and its live Q rows, packed on the device ----
+ * Everything a launch leaves behind is the per-env state, the key set and the Q block of each env.  A capture of n
+ * listed envs takes, per env in list order: one state record of state_bytes bytes; the key set ([touched_words]
+ * words, as stored); and only the LIVE rows of its Q block.  Row r of an env is live when its key-set bit is set or
+ * any of its cells differs from default_q as a 64-bit pattern (-0.0 under default_q = 0.0 is live; so is a NaN).
+ *   row_ids[row_off[k] .. row_off[k + 1]): the live rows of the k-th listed env, ascending.
+ *   cells[cell_off[k] .. cell_off[k + 1]): their cells as bit patterns, rows in row_ids order, a row's q_w cells in
+ *     stored order.
+ *   A state record: the env's slice of every per-env state array except the Q block and the key set, in a fixed
+ *     order, each array at an offset aligned to its element size, the record padded to a multiple of 8 bytes.  It
+ *     holds the env's seed (a uint64 at seed_offset), its epsilon-greedy stream, its interaction counts (the schedule
+ *     position), the pending-update slots and the episode state.  Its byte layout depends on the layout class of the
+ *     handle's kernel -- SFL_STATE_LANE (one env per lane, sfl_counters.kernel_variant == 0, and the host build) or
+ *     SFL_STATE_WAVE (every wave kernel) -- and a record is restored into a handle of the same class only.
+ *   The bytes do not depend on block scheduling: two captures of an unchanged handle are identical.
+ * sfl_state_info: the sizes, the layout class and the fingerprint of what a record depends on (the map descriptor,
+ *   gamma, default_q, ntab, max_steps, delay_threshold, which malfunction stream is set, the layout class).
+ * sfl_state_capture counts (device passes; the live bitmap and the offsets stay on the device) and returns the
+ *   offsets, with which the caller sizes the buffers of sfl_state_read, which gathers, copies out (a NULL pointer
+ *   skips one) and releases the device buffers.  A second sfl_state_capture replaces a pending one.
+ * sfl_state_restore writes n records into n listed slots: each slot's Q block becomes default_q plus the record's
+ *   rows, its key set and state arrays the record's, and the handle's host copy of the seeds follows.  No other env
+ *   is touched.  The epsilon / lr schedule tables (sfl_hparams, sfl_set_hparam_groups) and a Flatland malfunction
+ *   table (sfl_set_mf_schedule, indexed by slot) are the handle's, not the record's: the caller keeps them in step.
+ *   Not state: sfl_counters.decisions and a running curve's cells.
+ * sfl_state_ms: device time of the last capture (count + gather kernels) and of the last restore (0 on the host build).
+ * Refused, with the handle unchanged (everything is checked on the host before the first device write): a
+ *   graph-partitioned handle, one in external-action mode, an evaluation handle; an env or slot out of range or listed
+ *   twice; sfl_state_read without a pending capture; a layout class or fingerprint other than the handle's; row_off /
+ *   cell_off that do not start at 0, decrease, or do not end at n_rows / n_cells; a row id >= rows_per_env or not
+ *   strictly ascending within an env; an env whose cell count is not the sum of its rows' widths. */
+#define SFL_STATE_LANE 0u
+#define SFL_STATE_WAVE 1u
+typedef struct {
+  uint64_t fingerprint;
+  uint64_t q_per_env;
+  uint32_t state_bytes;     /* bytes of one env's state record */
+  uint32_t layout;          /* SFL_STATE_LANE or SFL_STATE_WAVE */
+  uint32_t touched_words;
+  uint32_t rows_per_env;
+  uint32_t seed_offset;     /* byte offset of the env's seed (uint64) in its record */
+  uint32_t pad_;
+} sfl_state_desc;
+int sfl_state_info(sfl_handle* h, sfl_state_desc* out);
+int sfl_state_capture(sfl_handle* h, uint32_t n, const uint32_t* envs, uint64_t* row_off /* [n + 1] */,
+                      uint64_t* cell_off /* [n + 1] */);
+int sfl_state_read(sfl_handle* h, uint8_t* state /* [n][state_bytes] */, uint32_t* touched /* [n][touched_words] */,
+                   uint32_t* row_ids /* [row_off[n]] */, uint64_t* cells /* [cell_off[n]] */);
+int sfl_state_restore(sfl_handle* h, uint64_t fingerprint, uint32_t layout, uint32_t n, const uint32_t* slots,
+                      const uint8_t* state, const uint32_t* touched, const uint64_t* row_off, const uint32_t* row_ids,
+                      uint64_t n_rows, const uint64_t* cell_off, const uint64_t* cells, uint64_t n_cells);
+int sfl_state_ms(sfl_handle* h, double* capture_ms, double* restore_ms /* either may be NULL */);
 #ifdef __cplusplus
 }
 #endif

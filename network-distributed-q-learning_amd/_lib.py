@@ -104,6 +104,14 @@ class EvalOut(C.Structure):
                 ("delays", P(C.c_int32)), ("at_dest", P(C.c_uint8))]
 
 
+class StateDesc(C.Structure):
+    """sfl_state_desc: what sfl_state_info reports of a handle's state records."""
+    _fields_ = [("fingerprint", C.c_uint64), ("q_per_env", C.c_uint64), ("state_bytes", C.c_uint32),
+                ("layout", C.c_uint32), ("touched_words", C.c_uint32), ("rows_per_env", C.c_uint32),
+                ("seed_offset", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+STATE_LAYOUTS = ("lane", "wave")  # include/sfl.h SFL_STATE_LANE, SFL_STATE_WAVE
 OBS_WIDTH = 18    # include/sfl.h SFL_OBS_WIDTH
 MAX_ACTIONS = 16  # include/sfl.h SFL_MAX_ACTIONS
 
@@ -182,6 +190,14 @@ EXPORTS = {
     "sfl_bank_eval": (C.c_int, [C.c_void_p, P(C.c_uint32), P(EvalOut)]),
     "sfl_bank_read": (C.c_int, [C.c_void_p, P(C.c_int64)]),
     "sfl_bank_fold_ms": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double)]),
+    # suspend and resume (runtime.Batch capture / restore / q_dicts)
+    "sfl_state_info": (C.c_int, [C.c_void_p, P(StateDesc)]),
+    "sfl_state_capture": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_uint32), P(C.c_uint64), P(C.c_uint64)]),
+    "sfl_state_read": (C.c_int, [C.c_void_p, P(C.c_uint8), P(C.c_uint32), P(C.c_uint32), P(C.c_uint64)]),
+    "sfl_state_restore": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_uint8),
+                                    P(C.c_uint32), P(C.c_uint64), P(C.c_uint32), C.c_uint64, P(C.c_uint64),
+                                    P(C.c_uint64), C.c_uint64]),
+    "sfl_state_ms": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double)]),
 }
 
 

@@ -846,6 +846,22 @@ struct HipBackend {
     check(hipEventRecord(ev1, stream), "event");
     return err.empty() ? 0 : -1;
   }
+  // sfl_state_*: one phase's kernels of sfl_snap.hip on the handle's stream, timed between the two events
+  int snap(const sfl::SnapArgs& a, int phase, float* ms) {
+    check(hipEventRecord(ev0, stream), "event");
+    const char* what = "";
+    int code = 0;
+    if (sfl::snap_launch(a, phase, (void*)stream, &what, &code)) {
+      if (err.empty()) err = std::string(what) + ": " + hipGetErrorString((hipError_t)code);
+      return -1;
+    }
+    check(hipEventRecord(ev1, stream), "event");
+    if (!check(event_wait(ev1), "sfl_state kernels")) return -1;
+    float t = 0.f;
+    hipEventElapsedTime(&t, ev0, ev1);
+    *ms = t;
+    return err.empty() ? 0 : -1;
+  }
   int sync() { return check(stream_wait(), "sync") && err.empty() ? 0 : -1; }
   // process-wide, one per device, built on first use and kept for the life of the process
   // SFL_SEEDSEQ_TABLE=0 (read on every call) runs without it, as a device that cannot hold its 8.6 GB does

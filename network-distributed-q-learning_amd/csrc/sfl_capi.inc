@@ -417,4 +417,35 @@ int sfl_bank_fold_ms(sfl_handle* h, double* last_ms, double* total_ms) {
   return 0;
 }
 
+// ---- suspend and resume (sfl_snap.h) ----
+int sfl_state_info(sfl_handle* h, sfl_state_desc* out) {
+  if (!h) return sfl::fail("sfl_state_info: null handle");
+  return sfl::state_info(HH(h), out);
+}
+
+int sfl_state_capture(sfl_handle* h, uint32_t n, const uint32_t* envs, uint64_t* row_off, uint64_t* cell_off) {
+  if (!h) return sfl::fail("sfl_state_capture: null handle");
+  return sfl::state_capture(HH(h), n, envs, row_off, cell_off);
+}
+
+int sfl_state_read(sfl_handle* h, uint8_t* state, uint32_t* touched, uint32_t* row_ids, uint64_t* cells) {
+  if (!h) return sfl::fail("sfl_state_read: null handle");
+  return sfl::state_read(HH(h), state, touched, row_ids, cells);
+}
+
+int sfl_state_restore(sfl_handle* h, uint64_t fingerprint, uint32_t layout, uint32_t n, const uint32_t* slots,
+                      const uint8_t* state, const uint32_t* touched, const uint64_t* row_off, const uint32_t* row_ids,
+                      uint64_t n_rows, const uint64_t* cell_off, const uint64_t* cells, uint64_t n_cells) {
+  if (!h) return sfl::fail("sfl_state_restore: null handle");
+  return sfl::state_restore(HH(h), fingerprint, layout, n, slots, state, touched, row_off, row_ids, n_rows, cell_off, cells,
+                            n_cells);
+}
+
+int sfl_state_ms(sfl_handle* h, double* capture_ms, double* restore_ms) {
+  if (!h) return sfl::fail("sfl_state_ms: null handle");
+  if (capture_ms) *capture_ms = HH(h)->snap.capture_ms;
+  if (restore_ms) *restore_ms = HH(h)->snap.restore_ms;
+  return 0;
+}
+
 }  // extern "C"

@@ -20,6 +20,7 @@
 #include "sfl_eval.h"
 #include "sfl_mfgen.h"
 #include "sfl_part.h"
+#include "sfl_snap.h"
 
 namespace sfl {
 
@@ -28,6 +29,46 @@ static thread_local std::string g_last_error;
 inline int fail(const std::string& msg) {
   g_last_error = msg;
   return -1;
+}
+
+// FNV-1a over bytes: the fingerprints of sfl_state_info (a state record names cells, rows, ports and trains of its map)
+inline uint64_t snap_hash(uint64_t h, const void* p, size_t n) {
+  const uint8_t* b = (const uint8_t*)p;
+  for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 0x100000001B3ull;
+  return h;
+}
+inline uint64_t snap_map_fp(const sfl_map_desc* md) {
+  uint64_t h = 0xCBF29CE484222325ull;
+  const size_t HW = (size_t)md->H * md->W, NP = (size_t)md->S * 4, S = md->S, T = md->T;
+  const int64_t sc[] = {md->H, md->W, md->S, md->T, md->K, md->max_episode_steps, md->mf_min, md->mf_max,
+                        (int64_t)md->q_per_env, (int64_t)md->rows_per_env};
+  h = snap_hash(h, sc, sizeof sc);
+  h = snap_hash(h, &md->mf_rate, 8);
+  auto arr = [&](const void* p, size_t bytes) { h = snap_hash(snap_hash(h, &bytes, sizeof bytes), p, bytes); };
+  arr(md->grid, HW * 2);
+  arr(md->cell_sw, HW * 2);
+  arr(md->sw_np, S);
+  arr(md->sw_na, S);
+  arr(md->act_src, S * 8);
+  arr(md->act_dst, S * 8);
+  arr(md->act_turn, S * 8);
+  arr(md->act_j, S * 8);
+  arr(md->first_other, NP);
+  arr(md->port_side, NP);
+  arr(md->slot_nroutes, NP);
+  arr(md->slot_route_act, NP * 4);
+  arr(md->q_w, NP);
+  arr(md->port_nb, NP * 2);
+  arr(md->port_len, NP * 2);
+  arr(md->port_unique, NP * 2);
+  arr(md->q_off, NP * 8);
+  arr(md->row_base, NP * 4);
+  arr(md->dist, (size_t)md->K * HW * 4 * 4);
+  for (const int32_t* p : {md->tr_ed, md->tr_la, md->tr_k, md->tr_target, md->tr_init_cell, md->tr_init_dist, md->tr_init_delay})
+    arr(p, T * 4);
+  arr(md->tr_init_dir, T);
+  arr(md->tr_init_port, T * 2);
+  return h;
 }
 
 template <class B>
@@ -120,6 +161,21 @@ struct Handle {
     float last_ms = 0.f;
     double total_ms = 0.0;
   } bank;
+  // suspend and resume (sfl_state_*; sfl_snap.h): the fingerprint of the map descriptor (create), each
+  // row's first cell and width on the host and the device (built at the first call), the pending capture between
+  // sfl_state_capture and sfl_state_read (its device buffers in bufs), and the device time of the last calls
+  struct Snap {
+    uint64_t map_fp = 0;
+    std::vector<uint8_t> row_w;
+    std::vector<uint64_t> row_cell;
+    uint8_t* d_row_w = nullptr;
+    uint64_t* d_row_cell = nullptr;
+    bool pending = false;
+    SnapArgs a{};
+    uint64_t n_rows = 0, n_cells = 0;
+    std::vector<void*> bufs;
+    float capture_ms = 0.f, restore_ms = 0.f;
+  } snap;
 
   template <class T>
   T* dalloc(size_t n) {
@@ -145,6 +201,7 @@ struct Handle {
       }
   }
   ~Handle() {
+    for (void* p : snap.bufs) be.free(p);
     for (void* p : allocs) be.free(p);
   }
 };
@@ -567,6 +624,12 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
   h->be.memset(s.tr_dec, 0, T * E * 2);
   h->be.memset(s.tr_delay, 0, T * E * 4);
   h->be.memset(s.own_n, 0, T * E);
+  // (never read before they are written; zeroed so that a state record, sfl_state_capture, is a function of the run
+  // and not of what the allocator handed out: the wave kernels never write these four)
+  h->be.memset(s.own, 0, T * OWN_MAX * E * 2);
+  h->be.memset(s.sc_desired, 0, T * E * 4);
+  h->be.memset(s.sc_pred, 0, T * E * 4);
+  h->be.memset(s.sc_aux, 0, T * E * 4);
   h->be.memset(s.occ, 0xFF, HW * E);
   h->be.memset(s.claim, 0xFF, HW * E);
   h->be.memset(s.sem, 0, NP * E * 8);
@@ -582,6 +645,7 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
     h->be.memset(bk.policy, 0, E * 4);
   }
   h->seeds.assign(env_seeds, env_seeds + E);
+  h->snap.map_fp = snap_map_fp(md);
   h->be.h2d(s.seed, env_seeds, E * 8);
   if (int rc = h->be.sync()) {
     delete h;
@@ -1959,6 +2023,345 @@ int curve_rounds(Handle<B>* h, int32_t* out) {
   if (!out) return fail("sfl_curve_rounds: null argument");
   h->be.d2h(out, h->cv.xa.mark, (size_t)h->E * 4);
   return h->be.sync() ? fail(h->be.error()) : 0;
+}
+
+// ---------------------------------------------------------------------------
+// suspend and resume (include/sfl.h sfl_state_*; sfl_snap.h)
+// ---------------------------------------------------------------------------
+// The env's record: every SflState array except q / touched, in declaration order, each at an offset aligned to its
+// element size; the layout class decides which arrays are env-major (sfl_wave.h tix / pix / cix, slot_ix) and that the
+// semaphore records are the wave kernels' 32-bit ones.  Returns the record's bytes (a multiple of 8).
+template <class B>
+uint32_t snap_fields(Handle<B>* h, SnapField* f, uint32_t* n_fields, uint32_t* seed_off) {
+  const SflState& s = h->st;
+  const SflMap& m = h->map;
+  const uint32_t T = (uint32_t)m.T, S = (uint32_t)m.S, NP = (uint32_t)m.NP, HW = (uint32_t)m.HW;
+  const uint32_t wave = h->variant > 0 ? 1u : 0u;
+  uint32_t n = 0, off = 0;
+  auto add = [&](void* base, uint32_t elem, uint32_t count, uint32_t major) {
+    off = (off + elem - 1u) / elem * elem;
+    f[n++] = SnapField{base, elem, count, major, off};
+    off += elem * count;
+  };
+  add(s.phase, 4, 1, 0);
+  add(s.elapsed, 4, 1, 0);
+  add(s.eflags, 4, 1, 0);
+  add(s.ep_t, 4, 1, 0);
+  add(s.n_test, 4, 1, 0);
+  add(s.epoch, 4, 1, 0);
+  add(s.rng, 8, 5, 0);
+  *seed_off = (off + 7u) / 8u * 8u;
+  add(s.seed, 8, 1, 0);
+  add(s.cum_reward, 8, 1, 0);
+  add(s.n_mf, 4, 1, 0);
+  add(s.ep_dec, 4, 1, 0);
+  add(s.ep_ticks, 4, 1, 0);
+  add(s.step_ctr, 8, 1, 0);
+  add(s.dec_total, 8, 1, 0);
+  add(s.masks, 4, 4 * MAXW, 0);
+  add(s.err, 4, 1, 0);
+  add(s.tr_pos, 4, T, wave);
+  add(s.tr_bits, 4, T, wave);
+  add(s.tr_plan, 4, T, wave);
+  add(s.tr_next, 2, T, wave);
+  add(s.tr_prev, 2, T, wave);
+  add(s.tr_src, 2, T, wave);
+  add(s.tr_dec, 2, T, wave);
+  add(s.tr_delay, 4, T, wave);
+  // (the lane body's ownership lists, tick scratch and cell maps: the wave kernels never touch them)
+  add(s.own, 2, T * OWN_MAX, 0);
+  add(s.own_n, 1, T, 0);
+  add(s.sc_desired, 4, T, 0);
+  add(s.sc_pred, 4, T, 0);
+  add(s.sc_aux, 4, T, 0);
+  add(s.occ, 1, HW, 0);
+  add(s.claim, 1, HW, 0);
+  if (wave) add(s.sem, 4, NP, 1);  // (32-bit records [E][NP] in the array sized for the 64-bit ones)
+  else add(s.sem, 8, NP, 0);
+  add(s.slot, 8, S * T, wave);
+  add(s.counts, 4, S, wave);
+  static_assert(SNAP_MAX_FIELDS >= 35, "fields");
+  *n_fields = n;
+  return (off + 7u) / 8u * 8u;
+}
+
+template <class B>
+uint64_t snap_fingerprint(Handle<B>* h) {
+  const SflMap& m = h->map;
+  uint64_t fp = snap_hash(0xCBF29CE484222325ull, &h->snap.map_fp, 8);
+  fp = snap_hash(fp, &m.gamma, 8);
+  fp = snap_hash(fp, &m.default_q, 8);
+  const int64_t sc[] = {m.ntab, m.max_steps, m.delay_thr, m.mf_steps > 0 ? 1 : 0, h->variant > 0 ? 1 : 0};
+  return snap_hash(fp, sc, sizeof sc);
+}
+
+template <class B>
+int snap_refuse(Handle<B>* h, const std::string& fn) {
+  if (h->bank.on) return fail(fn + ": an evaluation handle has no per-env table (sfl_create_eval)");
+  if (h->part.world) return fail(fn + ": the handle is graph-partitioned (its tables are owned rows)");
+  if (h->env_mode) return fail(fn + ": the handle is in external-action mode (no learner)");
+  if (h->map.q_per_env >= (1ull << 32)) return fail(fn + ": Q-table beyond 2^32 cells per env");
+  return 0;
+}
+
+// each row's first cell and width, as k_qinit derives them: block g holds rows row_base[g] + state, q_w[g] cells each
+template <class B>
+int snap_tables(Handle<B>* h, const std::string& fn) {
+  typename Handle<B>::Snap& sn = h->snap;
+  if (sn.d_row_w) return 0;
+  const SflMap& m = h->map;
+  const uint32_t rows = m.rows_per_env;
+  sn.row_w.assign(rows ? rows : 1, 0);
+  sn.row_cell.assign(rows ? rows : 1, 0);
+  for (int s = 0; s < m.S; ++s)
+    for (int i = 0; i < (int)h->h_sw_np[s]; ++i) {
+      const size_t g = (size_t)s * 4 + i;
+      const uint64_t w = h->h_q_w[g], nrows = ((uint64_t)1 << h->h_sw_np[s]) * (uint64_t)m.K * 3u;
+      if (w == 0) continue;
+      if (w > 4 || h->h_q_off[g] + nrows * w > m.q_per_env || h->h_row_base[g] + nrows > rows)
+        return fail(fn + ": a Q block lies outside the env's table (map compiler mismatch)");
+      for (uint64_t r = 0; r < nrows; ++r) {
+        sn.row_w[h->h_row_base[g] + r] = (uint8_t)w;
+        sn.row_cell[h->h_row_base[g] + r] = h->h_q_off[g] + r * w;
+      }
+    }
+  uint8_t* dw = (uint8_t*)h->upload(sn.row_w.data(), sn.row_w.size());
+  uint64_t* dc = (uint64_t*)h->upload(sn.row_cell.data(), sn.row_cell.size());
+  if (!dw || !dc || h->be.sync()) {
+    if (dw) h->dfree(dw);
+    if (dc) h->dfree(dc);
+    return fail(fn + ": device allocation failed (row table)");
+  }
+  sn.d_row_w = dw;
+  sn.d_row_cell = dc;
+  return 0;
+}
+
+template <class B>
+void snap_drop(Handle<B>* h) {
+  for (void* p : h->snap.bufs) h->be.free(p);
+  h->snap.bufs.clear();
+  h->snap.pending = false;
+}
+
+template <class B>
+void snap_args(Handle<B>* h, SnapArgs& a, uint32_t n) {
+  const SflMap& m = h->map;
+  a = SnapArgs{};
+  a.E = h->E;
+  a.n = n;
+  a.tw = m.touched_words;
+  a.rows = m.rows_per_env;
+  a.groups = (m.rows_per_env + SNAP_GROUP - 1) / SNAP_GROUP;
+  uint32_t seed_off = 0;
+  a.state_bytes = snap_fields(h, a.fields, &a.n_fields, &seed_off);
+  a.Q = m.q_per_env;
+  a.default_bits = cons_bits(m.default_q);
+  a.q = (uint64_t*)h->st.q;
+  a.touched = h->st.touched;
+  a.row_cell = h->snap.d_row_cell;
+  a.row_w = h->snap.d_row_w;
+}
+
+template <class B>
+int state_info(Handle<B>* h, sfl_state_desc* out) {
+  if (!out) return fail("sfl_state_info: null argument");
+  if (int rc = snap_refuse(h, "sfl_state_info")) return rc;
+  SnapField f[SNAP_MAX_FIELDS];
+  uint32_t nf = 0, seed_off = 0;
+  memset(out, 0, sizeof *out);
+  out->state_bytes = snap_fields(h, f, &nf, &seed_off);
+  out->seed_offset = seed_off;
+  out->fingerprint = snap_fingerprint(h);
+  out->q_per_env = h->map.q_per_env;
+  out->layout = h->variant > 0 ? SFL_STATE_WAVE : SFL_STATE_LANE;
+  out->touched_words = h->map.touched_words;
+  out->rows_per_env = h->map.rows_per_env;
+  return 0;
+}
+
+// a list of envs / slots: in range, none twice
+template <class B>
+int snap_list(Handle<B>* h, const std::string& fn, const char* what, uint32_t n, const uint32_t* list) {
+  if (n && !list) return fail(fn + ": null " + what + " list");
+  if (n > h->E) return fail(fn + ": " + std::to_string(n) + " " + what + "s listed, the handle has " + std::to_string(h->E));
+  std::vector<uint8_t> seen(h->E, 0);
+  for (uint32_t k = 0; k < n; ++k) {
+    if (list[k] >= h->E)
+      return fail(fn + ": " + what + " " + std::to_string(list[k]) + " out of range (n_envs = " + std::to_string(h->E) + ")");
+    if (seen[list[k]]) return fail(fn + ": " + what + " " + std::to_string(list[k]) + " is listed twice");
+    seen[list[k]] = 1;
+  }
+  return 0;
+}
+
+template <class B>
+int state_capture(Handle<B>* h, uint32_t n, const uint32_t* envs, uint64_t* row_off, uint64_t* cell_off) {
+  const std::string fn = "sfl_state_capture";
+  if (!row_off || !cell_off) return fail(fn + ": null argument");
+  if (int rc = snap_refuse(h, fn)) return rc;
+  if (int rc = snap_list(h, fn, "env", n, envs)) return rc;
+  if (int rc = snap_tables(h, fn)) return rc;
+  typename Handle<B>::Snap& sn = h->snap;
+  snap_drop(h);
+  SnapArgs& a = sn.a;
+  snap_args(h, a, n);
+  bool ok = true;
+  auto buf = [&](size_t bytes) -> void* {
+    void* p = h->be.alloc(bytes ? bytes : 1);
+    if (p) sn.bufs.push_back(p);
+    ok = ok && p;
+    return p;
+  };
+  uint32_t* d_envs = (uint32_t*)buf((size_t)n * 4);
+  a.envs = d_envs;
+  a.live = (uint32_t*)buf((size_t)n * a.tw * 4);
+  a.grp_rows = (uint32_t*)buf((size_t)n * a.groups * 4);
+  a.grp_cells = (uint32_t*)buf((size_t)n * a.groups * 4);
+  a.row_off = (uint64_t*)buf(((size_t)n + 1) * 8);
+  a.cell_off = (uint64_t*)buf(((size_t)n + 1) * 8);
+  if (!ok) {
+    snap_drop(h);
+    return fail(fn + ": device allocation failed");
+  }
+  row_off[0] = cell_off[0] = 0;
+  float ms = 0.f;
+  if (n) {
+    h->be.h2d(d_envs, envs, (size_t)n * 4);
+    int rc = h->be.snap(a, SNAP_COUNT, &ms);
+    if (!rc) {
+      h->be.d2h(row_off, a.row_off, ((size_t)n + 1) * 8);
+      h->be.d2h(cell_off, a.cell_off, ((size_t)n + 1) * 8);
+    }
+    if (h->be.sync()) rc = -1;  // (the host source of the env list lives until here)
+    if (rc) {
+      snap_drop(h);
+      return fail(fn + ": " + h->be.error());
+    }
+  }
+  sn.n_rows = row_off[n];
+  sn.n_cells = cell_off[n];
+  sn.capture_ms = ms;
+  sn.pending = true;
+  return 0;
+}
+
+template <class B>
+int state_read(Handle<B>* h, uint8_t* state, uint32_t* touched, uint32_t* row_ids, uint64_t* cells) {
+  const std::string fn = "sfl_state_read";
+  typename Handle<B>::Snap& sn = h->snap;
+  if (!sn.pending) return fail(fn + ": no pending capture (sfl_state_capture)");
+  SnapArgs& a = sn.a;
+  const size_t n = a.n;
+  bool ok = true;
+  auto buf = [&](size_t bytes) -> void* {
+    void* p = h->be.alloc(bytes ? bytes : 1);
+    if (p) sn.bufs.push_back(p);
+    ok = ok && p;
+    return p;
+  };
+  a.row_ids = (uint32_t*)buf(sn.n_rows * 4);
+  a.cells = (uint64_t*)buf(sn.n_cells * 8);
+  a.keys = (uint32_t*)buf(n * a.tw * 4);
+  a.state = (uint8_t*)buf(n * a.state_bytes);
+  int rc = ok ? 0 : -1;
+  float ms = 0.f;
+  if (ok && n) {
+    h->be.memset(a.state, 0, n * a.state_bytes);  // (the alignment gaps of a record read as zero)
+    rc = h->be.snap(a, SNAP_GATHER, &ms);
+    if (!rc) {
+      if (state) h->be.d2h(state, a.state, n * a.state_bytes);
+      if (touched) h->be.d2h(touched, a.keys, n * a.tw * 4);
+      if (row_ids && sn.n_rows) h->be.d2h(row_ids, a.row_ids, sn.n_rows * 4);
+      if (cells && sn.n_cells) h->be.d2h(cells, a.cells, sn.n_cells * 8);
+    }
+    if (h->be.sync()) rc = -1;
+  }
+  snap_drop(h);
+  if (!ok) return fail(fn + ": device allocation failed");
+  if (rc) return fail(fn + ": " + h->be.error());
+  sn.capture_ms += ms;
+  return 0;
+}
+
+template <class B>
+int state_restore(Handle<B>* h, uint64_t fingerprint, uint32_t layout, uint32_t n, const uint32_t* slots,
+                  const uint8_t* state, const uint32_t* touched, const uint64_t* row_off, const uint32_t* row_ids,
+                  uint64_t n_rows, const uint64_t* cell_off, const uint64_t* cells, uint64_t n_cells) {
+  const std::string fn = "sfl_state_restore";
+  if (int rc = snap_refuse(h, fn)) return rc;
+  const uint32_t mine = h->variant > 0 ? SFL_STATE_WAVE : SFL_STATE_LANE;
+  auto cls = [](uint32_t c) { return c == SFL_STATE_WAVE ? "wave" : c == SFL_STATE_LANE ? "lane" : "unknown"; };
+  if (layout != mine)
+    return fail(fn + ": a record of the " + cls(layout) + " layout class into a handle of the " + cls(mine) +
+                " class (records are restored into their own layout class only)");
+  if (fingerprint != snap_fingerprint(h))
+    return fail(fn + ": fingerprint mismatch: the record was taken with another map, gamma, default_q, ntab, max_steps, "
+                     "delay_threshold or malfunction stream than this handle's");
+  if (int rc = snap_list(h, fn, "slot", n, slots)) return rc;
+  if (n == 0) return 0;
+  if (!state || !touched || !row_off || !cell_off || (n_rows && !row_ids) || (n_cells && !cells))
+    return fail(fn + ": null argument");
+  if (int rc = snap_tables(h, fn)) return rc;
+  typename Handle<B>::Snap& sn = h->snap;
+  SnapArgs a;
+  snap_args(h, a, n);
+  if (row_off[0] != 0 || cell_off[0] != 0) return fail(fn + ": row_off / cell_off do not start at 0");
+  for (uint32_t k = 0; k < n; ++k)
+    if (row_off[k + 1] < row_off[k] || cell_off[k + 1] < cell_off[k])
+      return fail(fn + ": row_off / cell_off decrease at record " + std::to_string(k));
+  if (row_off[n] != n_rows || cell_off[n] != n_cells)
+    return fail(fn + ": row_off / cell_off end at " + std::to_string(row_off[n]) + " rows / " + std::to_string(cell_off[n]) +
+                " cells, the buffers hold " + std::to_string(n_rows) + " / " + std::to_string(n_cells));
+  std::vector<uint32_t> live((size_t)n * a.tw, 0u);
+  for (uint32_t k = 0; k < n; ++k) {
+    uint64_t nc = 0;
+    for (uint64_t j = row_off[k]; j < row_off[k + 1]; ++j) {
+      const uint32_t r = row_ids[j];
+      if (r >= a.rows)
+        return fail(fn + ": record " + std::to_string(k) + ": row id " + std::to_string(r) + " >= rows_per_env " +
+                    std::to_string(a.rows));
+      if (j > row_off[k] && r <= row_ids[j - 1])
+        return fail(fn + ": record " + std::to_string(k) + ": row ids not strictly ascending (" +
+                    std::to_string(row_ids[j - 1]) + " then " + std::to_string(r) + ")");
+      live[(size_t)k * a.tw + (r >> 5)] |= 1u << (r & 31u);
+      nc += sn.row_w[r];
+    }
+    if (nc != cell_off[k + 1] - cell_off[k])
+      return fail(fn + ": record " + std::to_string(k) + ": " + std::to_string(cell_off[k + 1] - cell_off[k]) +
+                  " cells, its rows' widths sum to " + std::to_string(nc));
+  }
+  // (validated: the first device write follows)
+  std::vector<void*> scratch;
+  auto up = [&](const void* src, size_t bytes) -> void* {
+    void* p = h->be.alloc(bytes ? bytes : 1);
+    scratch.push_back(p);
+    if (p && bytes && src) h->be.h2d(p, src, bytes);
+    return p;
+  };
+  a.envs = (const uint32_t*)up(slots, (size_t)n * 4);
+  a.live = (uint32_t*)up(live.data(), live.size() * 4);
+  a.grp_rows = (uint32_t*)up(nullptr, (size_t)n * a.groups * 4);
+  a.grp_cells = (uint32_t*)up(nullptr, (size_t)n * a.groups * 4);
+  a.row_off = (uint64_t*)up(row_off, ((size_t)n + 1) * 8);
+  a.cell_off = (uint64_t*)up(cell_off, ((size_t)n + 1) * 8);
+  a.cells = (uint64_t*)up(cells, n_cells * 8);
+  a.keys = (uint32_t*)up(touched, (size_t)n * a.tw * 4);
+  a.state = (uint8_t*)up(state, (size_t)n * a.state_bytes);
+  bool ok = true;
+  for (void* p : scratch) ok = ok && p;
+  float ms = 0.f;
+  int rc = ok ? h->be.snap(a, SNAP_RESTORE, &ms) : -1;
+  if (h->be.sync()) rc = -1;  // (the host sources of the uploads live until here)
+  for (void* p : scratch) h->be.free(p);
+  if (!ok) return fail(fn + ": device allocation failed");
+  if (rc) return fail(fn + ": " + h->be.error());
+  uint32_t nf = 0, seed_off = 0;
+  SnapField f[SNAP_MAX_FIELDS];
+  snap_fields(h, f, &nf, &seed_off);
+  for (uint32_t k = 0; k < n; ++k) memcpy(&h->seeds[slots[k]], state + (size_t)k * a.state_bytes + seed_off, 8);
+  sn.restore_ms = ms;
+  return 0;
 }
 
 }  // namespace sfl

@@ -105,6 +105,12 @@ struct HostBackend {
     sfl::eval_fold_host(a);
     return 0;
   }
+  // sfl_state_*: one phase as plain loops (sfl_snap.h)
+  int snap(const sfl::SnapArgs& a, int phase, float* ms) {
+    sfl::snap_host(a, phase);
+    *ms = 0.f;
+    return 0;
+  }
   int sync() { return 0; }
   uint64_t n_wait = 0;  // (nothing to wait for: the host build runs on the caller's thread)
   const uint32_t* seedseq_table() { return nullptr; }  // the host build draws every sub-generator

@@ -68,7 +68,8 @@ class DistrQLearning:
         return self.batch.q_dict(0)
 
     def q_tables(self) -> List[Dict[tuple, list]]:
-        return [self.batch.q_dict(e) for e in range(self.batch.E)]
+        """Every env's Q dict; more than one env: from one device capture of the live rows (Batch.q_dicts)."""
+        return self.batch.q_dicts() if self.batch.E > 1 else [self.batch.q_dict(0)]
 
     def _squeeze(self, a):
         return a[0] if self.batch.E == 1 else a
@@ -259,7 +260,7 @@ class DistrQLearning:
                 pickle.dump(self.consensus_table(consensus, cohorts, share=False), f)
             return
         envs = range(self.batch.E) if envs is None else envs
-        obj = self.batch.q_dict(envs[0]) if len(envs) == 1 else [self.batch.q_dict(e) for e in envs]
+        obj = self.batch.q_dict(envs[0]) if len(envs) == 1 else self.batch.q_dicts(envs)
         with open(filename, "wb") as f:
             pickle.dump(obj, f)
 

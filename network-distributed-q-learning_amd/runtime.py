@@ -57,6 +57,89 @@ def raw_to_dict(cm: CompiledMap, default_q: float, q: np.ndarray, touched: np.nd
     return out
 
 
+def row_widths(cm: CompiledMap) -> np.ndarray:
+    """Cells of every row id of the map's compact layout ([rows_per_env] uint8; 0 for a row id of no block): block
+    g = 4 * switch + in-port slot holds rows row_base[g] + state of q_w[g] cells each."""
+    A = cm.arrays
+    w = np.zeros(cm.rows_per_env, np.uint8)
+    for s in range(cm.S):
+        n = (1 << len(cm.ports[s])) * cm.K * 3
+        for slot in range(len(cm.ports[s])):
+            g = 4 * s + slot
+            w[int(A["row_base"][g]): int(A["row_base"][g]) + n] = int(A["q_w"][g])
+    return w
+
+
+def rows_to_dict(cm: CompiledMap, default_q: float, touched: np.ndarray, row_ids: np.ndarray, cells: np.ndarray,
+                 widths: Optional[np.ndarray] = None) -> Dict[tuple, list]:
+    """``raw_to_dict`` on one env's section of a capture (``Batch.capture``): its key-set words, its live row ids
+    (ascending) and their cells as uint64 bit patterns -- the same dict, in the same order, without the dense block.
+    A live row whose key bit is clear (values left there by set_q_raw or a shared consensus) is no dict entry, as in
+    ``raw_to_dict``.  ``widths``: ``row_widths(cm)``, to share between calls."""
+    widths = row_widths(cm) if widths is None else widths
+    row_ids = np.asarray(row_ids, np.int64)
+    vals = np.ascontiguousarray(cells, np.uint64).view(np.float64)
+    start = np.zeros(len(row_ids) + 1, np.int64)
+    np.cumsum(widths[row_ids], out=start[1:])
+    bits = np.unpackbits(np.ascontiguousarray(touched, np.uint32).view(np.uint8), bitorder="little")
+    keyed = bits[row_ids].astype(bool)
+    A = cm.arrays
+    dq = float(default_q)
+    out = {}
+    for s in range(cm.S):
+        nrows = (1 << len(cm.ports[s])) * cm.K * 3
+        for slot in range(len(cm.ports[s])):
+            g = 4 * s + slot
+            base = int(A["row_base"][g])
+            lo, hi = np.searchsorted(row_ids, (base, base + nrows))
+            if lo == hi or not keyed[lo:hi].any():
+                continue
+            routes = [a for a, (src, _) in enumerate(cm.outcomes[s]) if src == slot] + [int(cm.n_actions[s]) - 1]
+            na = int(cm.n_actions[s])
+            for i in np.nonzero(keyed[lo:hi])[0] + lo:
+                v = vals[start[i]: start[i + 1]]
+                full = [dq] * na
+                for j, a in enumerate(routes):
+                    full[a] = float(v[j])
+                out[cm.obs_of_row(s, slot, int(row_ids[i]) - base)] = full
+    return out
+
+
+class BatchState:
+    """A capture of some envs of a ``Batch`` (``Batch.capture``) as plain numpy arrays, n = the envs captured:
+    ``state`` [n][state_bytes] uint8 (one record per env: episode state, RNG, interaction counts, pending-update
+    slots, seed), ``touched`` [n][touched_words] uint32 (the key sets), ``row_off`` / ``cell_off`` [n + 1] uint64,
+    ``row_ids`` uint32 (each env's live Q rows, ascending) and ``cells`` uint64 (their cells as bit patterns);
+    ``seeds`` [n] uint64; ``sched`` [n][4] float64, the (epsilon, epsilon_decay_rate, lr, lr_decay_rate) each env
+    learns with; ``fingerprint`` (of the map, gamma, default_q, ntab, max_steps, delay_threshold, the malfunction
+    stream's kind and the layout class) and ``layout`` ("lane" or "wave": which kernels' record format)."""
+
+    ARRAYS = (("state", np.uint8), ("touched", np.uint32), ("row_off", np.uint64), ("row_ids", np.uint32),
+              ("cell_off", np.uint64), ("cells", np.uint64), ("seeds", np.uint64), ("sched", np.float64))
+
+    def __init__(self, fingerprint: int, layout: str, **arrays):
+        self.fingerprint = int(fingerprint)
+        self.layout = str(layout)
+        for name, dt in self.ARRAYS:
+            setattr(self, name, np.ascontiguousarray(arrays[name], dt))
+
+    def __len__(self):
+        return len(self.seeds)
+
+    def save(self, path) -> None:
+        """One uncompressed .npz written to exactly ``path``."""
+        with open(path, "wb") as f:
+            np.savez(f, fingerprint=np.array([self.fingerprint], np.uint64),
+                     layout=np.array([_lib.STATE_LAYOUTS.index(self.layout)], np.uint32),
+                     **{name: getattr(self, name) for name, _ in self.ARRAYS})
+
+    @classmethod
+    def load(cls, path) -> "BatchState":
+        with np.load(path, allow_pickle=False) as z:
+            return cls(int(z["fingerprint"][0]), _lib.STATE_LAYOUTS[int(z["layout"][0])],
+                       **{name: z[name] for name, _ in cls.ARRAYS})
+
+
 def dict_to_raw(cm: CompiledMap, default_q: float, table: Dict[tuple, list]) -> Tuple[np.ndarray, np.ndarray]:
     """Inverse of ``raw_to_dict`` (``DistrQLearning.load``): the reference's ``q_table`` dict as a compact Q block and
     key-set bitmap; rejects rows the compact layout cannot hold."""
@@ -528,6 +611,104 @@ class Batch:
     def q_dict(self, env: int) -> Dict[tuple, list]:
         """Touched rows as {observation tuple: [Q per action]} — the reference's ``q_table``."""
         return raw_to_dict(self.cm, self.hp["default_q"], *self.q_raw(env))
+
+    # ---- suspend and resume (sfl_state_*): per-env state and live Q rows, packed on the device ----
+    def state_info(self) -> dict:
+        d = _lib.StateDesc()
+        self.lib.check(self.lib.dll.sfl_state_info(self.h, C.byref(d)), "sfl_state_info")
+        return dict(fingerprint=int(d.fingerprint), q_per_env=int(d.q_per_env), state_bytes=int(d.state_bytes),
+                    layout=_lib.STATE_LAYOUTS[d.layout], touched_words=int(d.touched_words),
+                    rows_per_env=int(d.rows_per_env), seed_offset=int(d.seed_offset))
+
+    def state_ms(self) -> Tuple[float, float]:
+        """Device ms of the last capture (its count and gather kernels) and of the last restore."""
+        cap, res = C.c_double(0.0), C.c_double(0.0)
+        self.lib.check(self.lib.dll.sfl_state_ms(self.h, C.byref(cap), C.byref(res)), "sfl_state_ms")
+        return float(cap.value), float(res.value)
+
+    def _sched(self, e: int) -> List[float]:
+        """The four schedule values env e learns with: its group's, else the batch's own."""
+        src = self.hparam_groups[self.env_group[e]] if self.hparam_groups else self.hp
+        return [float(src[k]) for k in self.GROUP_KEYS]
+
+    def _env_list(self, envs, what):
+        ids = list(range(self.E)) if envs is None else [int(e) for e in envs]
+        if ids and (min(ids) < 0 or max(ids) > 0xFFFFFFFF):
+            raise ValueError(f"{what}: env indices must be non-negative")
+        return np.array(ids, dtype=np.uint32)
+
+    def _capture(self, envs, with_state: bool):
+        """(info, env list, state or None, touched, row_off, row_ids, cell_off, cells) of one device capture."""
+        info = self.state_info()
+        ids = self._env_list(envs, "capture")
+        n = len(ids)
+        row_off, cell_off = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+        self.lib.check(self.lib.dll.sfl_state_capture(self.h, n, _ptr(ids, C.c_uint32), _ptr(row_off, C.c_uint64),
+                                                      _ptr(cell_off, C.c_uint64)), "sfl_state_capture")
+        state = np.zeros((n, info["state_bytes"]), np.uint8) if with_state else None
+        touched = np.zeros((n, info["touched_words"]), np.uint32)
+        row_ids, cells = np.zeros(int(row_off[n]), np.uint32), np.zeros(int(cell_off[n]), np.uint64)
+        self.lib.check(self.lib.dll.sfl_state_read(self.h, _ptr(state, C.c_uint8) if with_state else None,
+                                                   _ptr(touched, C.c_uint32), _ptr(row_ids, C.c_uint32),
+                                                   _ptr(cells, C.c_uint64)), "sfl_state_read")
+        return info, ids, state, touched, row_off, row_ids, cell_off, cells
+
+    def capture(self, envs: Optional[Sequence[int]] = None) -> BatchState:
+        """Everything a launch leaves behind of ``envs`` (default: every env, in order): each env's state record, its
+        key set and the live rows of its Q block -- the rows whose key bit is set or that hold a cell other than
+        ``default_q`` as a bit pattern -- found and packed on the device (include/sfl.h sfl_state_capture).
+        ``restore`` continues them, in this batch or another, bit for bit as if they had never stopped.
+        NOT part of the state: ``counters()["decisions"]`` (a handle's own total) and a running curve's cells (start
+        a new curve after ``restore``).  The schedule tables are the batch's: the record carries each env's four
+        schedule values and ``restore`` checks them."""
+        info, ids, state, touched, row_off, row_ids, cell_off, cells = self._capture(envs, True)
+        so = info["seed_offset"]
+        seeds = np.ascontiguousarray(state[:, so: so + 8]).view(np.uint64).reshape(-1)
+        sched = np.array([self._sched(int(e)) for e in ids], np.float64).reshape(len(ids), 4)
+        return BatchState(info["fingerprint"], info["layout"], state=state, touched=touched, row_off=row_off,
+                          row_ids=row_ids, cell_off=cell_off, cells=cells, seeds=seeds, sched=sched)
+
+    def restore(self, state: BatchState, into: Optional[Sequence[int]] = None) -> None:
+        """Write the records of ``state`` into the slots ``into`` (default: 0 .. len(state) - 1) of this batch: each
+        slot's Q block becomes ``default_q`` plus the record's rows; its key set, env state, RNG stream, interaction
+        counts and seed the record's; ``self.seeds`` follows, and with ``malfunction_stream="flatland"`` the schedule is
+        expanded again for the new seeds and uploaded.  No other env changes.  Raises ``ValueError`` when a slot's
+        four schedule values (its group's, or ``hp``'s) differ bitwise from the ones the env was captured with -- the
+        record's interaction counts index those tables, so continuing on other schedules is not a resume -- and
+        ``SflError`` for what the library refuses (another map, gamma, default_q, ntab, max_steps, delay_threshold,
+        malfunction stream or layout class; a slot out of range or listed twice; inconsistent arrays), leaving the
+        batch unchanged.  A running curve does not carry over: call ``curve_begin`` after ``restore``."""
+        n = len(state)
+        slots = self._env_list(range(n) if into is None else into, "restore")
+        if len(slots) != n:
+            raise ValueError(f"restore: {len(slots)} slots for {n} records")
+        for k, e in enumerate(slots):
+            if int(e) < self.E:
+                mine = np.array(self._sched(int(e)), np.float64)
+                if not np.array_equal(mine.view(np.uint64), state.sched[k].view(np.uint64)):
+                    raise ValueError(f"restore: slot {int(e)} learns with (epsilon, epsilon_decay_rate, lr, lr_decay_rate) "
+                                     f"= {mine.tolist()}, record {k} was captured with {state.sched[k].tolist()}")
+        layout = _lib.STATE_LAYOUTS.index(state.layout)
+        self.lib.check(self.lib.dll.sfl_state_restore(
+            self.h, state.fingerprint, layout, n, _ptr(slots, C.c_uint32), _ptr(state.state, C.c_uint8),
+            _ptr(state.touched, C.c_uint32), _ptr(state.row_off, C.c_uint64), _ptr(state.row_ids, C.c_uint32),
+            len(state.row_ids), _ptr(state.cell_off, C.c_uint64), _ptr(state.cells, C.c_uint64), len(state.cells)),
+            "sfl_state_restore")
+        for k, e in enumerate(slots):
+            self.seeds[int(e)] = int(state.seeds[k])
+        if self.malfunction_stream == "flatland" and n:
+            tab = mfstream.schedule(self.lib, self.cm.scenario, self.seeds)
+            self.lib.check(self.lib.dll.sfl_set_mf_schedule(self.h, tab.shape[1], _ptr(tab, C.c_uint8)),
+                           "sfl_set_mf_schedule")
+
+    def q_dicts(self, envs: Optional[Sequence[int]] = None) -> List[Dict[tuple, list]]:
+        """``[q_dict(e) for e in envs]`` (default: every env) from one device capture: only the live rows leave the
+        device, not a dense block per env."""
+        _, ids, _, touched, row_off, row_ids, cell_off, cells = self._capture(envs, False)
+        w = row_widths(self.cm)
+        dq = self.hp["default_q"]
+        return [rows_to_dict(self.cm, dq, touched[k], row_ids[int(row_off[k]): int(row_off[k + 1])],
+                             cells[int(cell_off[k]): int(cell_off[k + 1])], w) for k in range(len(ids))]
 
     # ---- consensus Q-tables (sfl_consensus): a cohort's learners merged on the device, and shared ----
     def consensus(self, mode: str = "mean", cohorts: Optional[Sequence[Optional[int]]] = None,
