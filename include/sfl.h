@@ -34,6 +34,9 @@
  *   sfl_env_step_dev / sfl_env_sync   the same protocol for a policy on the device: device pointers in and
  *                     out, the observation vector of observer.py:269-308 decoded on the device, queued on the
  *                     caller's stream without a wait (the one call that is not synchronous)
+ *   sfl_env_trans_begin / sfl_env_trans_end   the learner's pending updates (update_dict, distr_q.py:322-356)
+ *                     kept on the device behind every env step: complete transitions appended to a replay
+ *                     ring in device memory
  *   sfl_consensus / sfl_get_consensus_q   no counterpart in the reference, whose learners are one process each:
  *                     the envs' Q-tables merged per cohort on the device (mean of the learned values, or the
  *                     optimistic max of distributed Q-learning), handed back to every member, and one consensus
@@ -318,6 +321,53 @@ typedef struct {
 } sfl_env_dev_io;
 int sfl_env_step_dev(sfl_handle* h, const sfl_env_dev_io* io);
 int sfl_env_sync(sfl_handle* h);
+/* ---- external-action mode: learner transitions assembled on the device ----
+ * A switch's action is credited later: its reward arrives with the next decision of the same train at the successor
+ * switch, or as the destination bonus when the train arrives (the reference's update_dict keyed (next_switch, train),
+ * distr_q.py:283, 322-356).  Between sfl_env_trans_begin and sfl_env_trans_end that bookkeeping runs on the device
+ * behind EVERY sfl_env_step and sfl_env_step_dev of the handle (the two may be mixed), on the same stream, and
+ * appends complete transitions to a replay ring the caller owns.  Per env, with (s, h, obs, r, mask) the decision the
+ * previous call emitted and a the action this call applied to it (a >= 0, not refused: next_switch >= 0):
+ *   1. if (s, h) is pending: the row {the entry's agent, obs, action; reward r; next_agent s, next_obs obs,
+ *      next_action_mask mask; terminal 0}, and the entry goes (after a STOP agent == next_agent: emitted like any other);
+ *   2. pending[(next_switch, h)] = (s, obs, a)   (an entry already there is overwritten);
+ *   3. for each train newly in `arrived`, in ascending order, each of its pending entries in ascending switch order:
+ *      the row {the entry's agent, obs, action; reward SFL_DEST_BONUS; next_agent -1, next_obs all -1, mask 0,
+ *      next_n_actions 0; terminal 1}, and the entry goes (this covers the entry step 2 just wrote);
+ *   4. if the episode ended in this call (agent == -1) or the action is SFL_ACTION_RESET: dropped[e] += the env's
+ *      pending entries, and the table empties (after 1-3 at an episode end; alone at a reset).
+ * A call that applies nothing to an env (a negative or null action, a refused action, the first call after begin)
+ * emits nothing for it.  Rows carry env, train and now of the entry's decision.  Order: calls in order, envs ascending
+ * within a call, the order above within an env.  Row g of the run (g = 0, 1, ...) lands in slot g % capacity; of a
+ * call with more than `capacity` rows only the last `capacity` are written.  total[0] counts all rows since begin
+ * and last_count[0] those of the last call; both live in device memory and are written (never read) by the kernels, so
+ * a consumer on the same stream needs no host round trip.  Every pointer is DEVICE memory (host memory on the host
+ * build); obs / next_obs / next_action_mask may be null (skipped) and must be 8- / 8- / 16-byte aligned, rows as
+ * sfl_env_step_dev's obs and action_mask.  sfl_env_trans_begin zeroes total, last_count and dropped and leaves the
+ * columns as they are; it fails on a handle that is not in external-action mode, on an evaluation handle, on a
+ * graph-partitioned handle and with capacity 0.  sfl_env_begin / sfl_env_begin_wave end a running assembler. */
+#define SFL_DEST_BONUS 1000 /* the learner's destination bonus (distr_q.py destination_bonus) */
+typedef struct {
+  uint32_t capacity; /* N, rows of the ring (1 .. 2^31 - 1) */
+  uint32_t pad_;
+  int32_t* env;            /* [N] */
+  int32_t* train;          /* [N] */
+  int32_t* now;            /* [N] elapsed ticks at the entry's decision */
+  int32_t* agent;          /* [N] the deciding switch */
+  int32_t* action;         /* [N] */
+  int32_t* reward;         /* [N] */
+  int32_t* next_agent;     /* [N] -1: terminal */
+  int32_t* next_n_actions; /* [N] Discrete(n) of next_agent; 0: terminal */
+  uint8_t* terminal;       /* [N] */
+  int32_t* obs;            /* [N][SFL_OBS_WIDTH] or null */
+  int32_t* next_obs;       /* [N][SFL_OBS_WIDTH] or null */
+  uint8_t* next_action_mask; /* [N][SFL_MAX_ACTIONS] or null */
+  int64_t* total;          /* [1] */
+  int32_t* last_count;     /* [1] */
+  int64_t* dropped;        /* [n_envs] */
+} sfl_env_trans_io;
+int sfl_env_trans_begin(sfl_handle* h, const sfl_env_trans_io* io);
+int sfl_env_trans_end(sfl_handle* h);
 /* the two coordinate tables the observation decode reads, as derived at sfl_create from cell_sw and from
  * tr_k / tr_target (debug / tests): switch_rc[S][2] and station_rc[K][2] as (row, column); null skips one */
 int sfl_get_obs_tables(sfl_handle* h, int32_t* switch_rc, int32_t* station_rc);

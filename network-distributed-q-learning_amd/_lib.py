@@ -122,6 +122,18 @@ class EnvDevIO(C.Structure):
                 ("done", P(C.c_uint8))]
 
 
+DEST_BONUS = 1000  # include/sfl.h SFL_DEST_BONUS
+
+
+class EnvTransIO(C.Structure):
+    """sfl_env_trans_io (external-action mode's transition ring, device pointers)."""
+    _fields_ = [("capacity", C.c_uint32), ("pad_", C.c_uint32), ("env", P(C.c_int32)), ("train", P(C.c_int32)),
+                ("now", P(C.c_int32)), ("agent", P(C.c_int32)), ("action", P(C.c_int32)), ("reward", P(C.c_int32)),
+                ("next_agent", P(C.c_int32)), ("next_n_actions", P(C.c_int32)), ("terminal", P(C.c_uint8)),
+                ("obs", P(C.c_int32)), ("next_obs", P(C.c_int32)), ("next_action_mask", P(C.c_uint8)),
+                ("total", P(C.c_int64)), ("last_count", P(C.c_int32)), ("dropped", P(C.c_int64))]
+
+
 EXPORTS = {
     "sfl_abi_version": (C.c_int, []),
     "sfl_build_id": (C.c_char_p, []),
@@ -145,6 +157,8 @@ EXPORTS = {
     "sfl_env_step": (C.c_int, [C.c_void_p, P(EnvIO)]),
     "sfl_env_step_dev": (C.c_int, [C.c_void_p, P(EnvDevIO)]),
     "sfl_env_sync": (C.c_int, [C.c_void_p]),
+    "sfl_env_trans_begin": (C.c_int, [C.c_void_p, P(EnvTransIO)]),
+    "sfl_env_trans_end": (C.c_int, [C.c_void_p]),
     "sfl_get_obs_tables": (C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_int32)]),
     "sfl_get_phase_cycles": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_int32]),
     "sfl_get_env_state": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_int32), P(C.c_int32), P(C.c_uint64),

@@ -26,6 +26,7 @@ from .compiler import CompiledMap
 from .runtime import Batch, _ptr
 
 # the learner's hyper-parameters do not enter the env (no epsilon draw, no Q-table access)
+DEST_BONUS = _lib.DEST_BONUS  # include/sfl.h SFL_DEST_BONUS: the reward of a terminal transition (transitions_begin)
 ACTION_RESET = -2  # include/sfl.h SFL_ACTION_RESET: reset the env where it stands (env.reset() mid-episode)
 _STREAM_DEFAULT = 1  # include/sfl.h SFL_STREAM_DEFAULT: the device's default stream (its own handle is null)
 _ENV_HP = dict(gamma=1.0, epsilon=0.0, epsilon_decay_rate=1.0, lr=0.0, lr_decay_rate=1.0, default_q=0.0)
@@ -81,6 +82,7 @@ class AECBatch:
         self._t = None            # step_torch's tensors and descriptor (made by its first call)
         self._stream = None       # the stream last handed to the library (step_torch on a HIP device)
         self._host_stale = False  # device steps ran since the host arrays (self.out) were last filled
+        self._trans = None        # the transition ring's tensors and descriptor (transitions_begin)
         try:
             if kernel == "wave":
                 self.lib.check(self.lib.dll.sfl_env_begin_wave(self.batch.h), "sfl_env_begin_wave")
@@ -122,6 +124,72 @@ class AECBatch:
         self._t = dict(out=out, dio=dio, dev=dev, on_gpu=on_gpu, none=torch.full((E,), -1, **i32), act=None)
         return self._t
 
+    def _follow_stream(self, torch, t):
+        if t["on_gpu"]:
+            # the library follows the stream the tensors are produced on (sfl_set_stream synchronises: only on a change)
+            s = torch.cuda.current_stream(t["dev"]).cuda_stream or _STREAM_DEFAULT
+            if s != self._stream:
+                self.lib.check(self.lib.dll.sfl_set_stream(self.batch.h, C.c_void_p(s)), "sfl_set_stream")
+                self._stream = s
+
+    # ---- learner transitions assembled on the device (include/sfl.h sfl_env_trans_*) ----------
+    TRANS_FIELDS = ("env", "train", "now", "agent", "action", "reward", "next_agent", "next_n_actions")
+
+    def transitions_begin(self, capacity: Optional[int] = None):
+        """Start the transition assembler: from now on every ``step`` / ``step_torch`` call is followed, on the device
+        and on the same stream, by the learner's bookkeeping (the reference's ``update_dict``, distr_q.py:322-356), which
+        appends complete transitions to a replay ring of ``capacity`` rows (default ``2 * E``).  Returns the ring, a dict
+        of tensors on the handle's device (CPU tensors with the host build), which ``transitions()`` returns too:
+        ``env``, ``train``, ``now``, ``agent``, ``action``, ``reward``, ``next_agent``, ``next_n_actions`` int32 [N];
+        ``terminal`` uint8 [N]; ``obs``, ``next_obs`` int32 [N, 18]; ``next_action_mask`` uint8 [N, 16]; ``total``
+        int64 [1] (rows since begin: row g is in slot ``g % N``), ``last_count`` int32 [1] (rows of the last call) and
+        ``dropped`` int64 [E] (pending entries discarded at episode ends and resets).  A row is
+        ``(agent, obs, action) -> reward, (next_agent, next_obs, next_action_mask)``; a terminal row (the train arrived)
+        has ``reward == DEST_BONUS``, ``terminal == 1``, ``next_agent == -1``, ``next_obs`` all -1 and a zero mask;
+        after a STOP ``agent == next_agent``.  Order: calls, envs ascending, and within an env the row of the deciding
+        train first, then the terminal rows by train and switch.  Nothing waits for the device; the tensors are
+        rewritten in place by later calls.  Sampling a minibatch without leaving the device::
+
+            ring = batch.transitions_begin(capacity=1 << 20)
+            ...                                        # out = batch.step_torch(policy(out)), many times
+            n = ring["total"].clamp(max=ring["env"].numel())          # rows that are valid, a tensor: no .item()
+            idx = torch.randint(0, 1 << 31, (256,), device=n.device) % n.clamp(min=1)
+            obs, act, rew = ring["obs"][idx], ring["action"][idx], ring["reward"][idx]
+            nobs, nmask, term = ring["next_obs"][idx], ring["next_action_mask"][idx], ring["terminal"][idx]
+        """
+        import torch
+        if capacity is None:
+            capacity = 2 * self.E
+        if not isinstance(capacity, int) or isinstance(capacity, bool) or capacity < 1 or capacity > 0x7FFFFFFF:
+            raise ValueError(f"transitions_begin: capacity {capacity!r} (an int of 1 .. 2^31 - 1)")
+        t = self._t or self._torch_setup(torch)
+        self._follow_stream(torch, t)
+        dev, N = t["dev"], capacity
+        ring = {k: torch.zeros(N, dtype=torch.int32, device=dev) for k in self.TRANS_FIELDS}
+        ring["terminal"] = torch.zeros(N, dtype=torch.uint8, device=dev)
+        ring["obs"] = torch.zeros((N, _lib.OBS_WIDTH), dtype=torch.int32, device=dev)
+        ring["next_obs"] = torch.zeros((N, _lib.OBS_WIDTH), dtype=torch.int32, device=dev)
+        ring["next_action_mask"] = torch.zeros((N, _lib.MAX_ACTIONS), dtype=torch.uint8, device=dev)
+        ring["total"] = torch.zeros(1, dtype=torch.int64, device=dev)
+        ring["last_count"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        ring["dropped"] = torch.zeros(self.E, dtype=torch.int64, device=dev)
+        io = _lib.EnvTransIO()
+        io.capacity = N
+        for k, ct in _lib.EnvTransIO._fields_[2:]:
+            setattr(io, k, C.cast(ring[k].data_ptr(), ct))
+        self.lib.check(self.lib.dll.sfl_env_trans_begin(self.batch.h, C.byref(io)), "sfl_env_trans_begin")
+        self._trans = dict(ring=ring, io=io)
+        return ring
+
+    def transitions(self):
+        """The ring ``transitions_begin`` returned (None: no assembler is running)."""
+        return self._trans["ring"] if self._trans else None
+
+    def transitions_end(self) -> None:
+        """Stop the assembler: later calls leave the ring as it is (the tensors stay valid)."""
+        self.lib.check(self.lib.dll.sfl_env_trans_end(self.batch.h), "sfl_env_trans_end")
+        self._trans = None
+
     def step_torch(self, actions=None):
         """``step`` for a policy that lives on the handle's device: ``actions`` is an int32 tensor [E] on that device
         (None: no actions), the result a dict of tensors on it -- the ``FIELDS`` of ``step`` (all int32: ``state``,
@@ -145,12 +213,7 @@ class AECBatch:
             if actions.device != t["dev"]:
                 raise ValueError(f"step_torch: actions on {actions.device}, the envs are on {t['dev']}")
             a = actions
-        if t["on_gpu"]:
-            # the library follows the stream the tensors are produced on (sfl_set_stream synchronises: only on a change)
-            s = torch.cuda.current_stream(t["dev"]).cuda_stream or _STREAM_DEFAULT
-            if s != self._stream:
-                self.lib.check(self.lib.dll.sfl_set_stream(self.batch.h, C.c_void_p(s)), "sfl_set_stream")
-                self._stream = s
+        self._follow_stream(torch, t)
         t["act"] = a  # (alive until the next call: the kernel reads it after this call returned)
         t["dio"].io.actions = C.cast(a.data_ptr(), _lib.P(C.c_int32))
         self._host_stale = True

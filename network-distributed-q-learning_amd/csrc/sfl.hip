@@ -862,6 +862,16 @@ struct HipBackend {
     *ms = t;
     return err.empty() ? 0 : -1;
   }
+  // sfl_env_trans_*: the two kernels of sfl_trans.hip queued behind the env step, without a wait
+  int trans(const sfl::TransArgs& a) {
+    const char* what = "";
+    int code = 0;
+    if (sfl::trans_launch(a, (void*)stream, &what, &code)) {
+      if (err.empty()) err = std::string(what) + ": " + hipGetErrorString((hipError_t)code);
+      return -1;
+    }
+    return err.empty() ? 0 : -1;
+  }
   int sync() { return check(stream_wait(), "sync") && err.empty() ? 0 : -1; }
   // process-wide, one per device, built on first use and kept for the life of the process
   // SFL_SEEDSEQ_TABLE=0 (read on every call) runs without it, as a device that cannot hold its 8.6 GB does

@@ -183,6 +183,16 @@ int sfl_env_sync(sfl_handle* h) {
   return sfl::env_sync(HH(h));
 }
 
+int sfl_env_trans_begin(sfl_handle* h, const sfl_env_trans_io* io) {
+  if (!h) return sfl::fail("sfl_env_trans_begin: null handle");
+  return sfl::trans_begin(HH(h), io);
+}
+
+int sfl_env_trans_end(sfl_handle* h) {
+  if (!h) return sfl::fail("sfl_env_trans_end: null handle");
+  return sfl::trans_end(HH(h));
+}
+
 int sfl_get_obs_tables(sfl_handle* h, int32_t* switch_rc, int32_t* station_rc) {
   if (!h) return sfl::fail("sfl_get_obs_tables: null handle");
   return sfl::get_obs_tables(HH(h), switch_rc, station_rc);

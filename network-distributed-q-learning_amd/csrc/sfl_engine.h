@@ -21,6 +21,7 @@
 #include "sfl_mfgen.h"
 #include "sfl_part.h"
 #include "sfl_snap.h"
+#include "sfl_trans.h"
 
 namespace sfl {
 
@@ -176,6 +177,14 @@ struct Handle {
     std::vector<void*> bufs;
     float capture_ms = 0.f, restore_ms = 0.f;
   } snap;
+  // external-action mode's transition assembler (sfl_env_trans_*; sfl_trans.h): on between
+  // sfl_env_trans_begin and sfl_env_trans_end (or the next sfl_env_begin); a holds the ring and the assembler's own
+  // state (allocated at the first begin), the step's buffers are filled in per call; parity: the cursor this call reads
+  struct Trans {
+    bool on = false;
+    TransArgs a{};
+    uint32_t parity = 0;
+  } tr;
 
   template <class T>
   T* dalloc(size_t n) {
@@ -1143,6 +1152,113 @@ inline int ext_variant(int v) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// external-action mode's transition assembler (include/sfl.h sfl_env_trans_*; sfl_trans.h)
+// ---------------------------------------------------------------------------
+template <class B>
+int trans_begin(Handle<B>* h, const sfl_env_trans_io* io) {
+  const char* fn = "sfl_env_trans_begin: ";
+  if (h->bank.on) return fail(std::string(fn) + "an evaluation handle has no external-action mode (sfl_create_eval)");
+  if (h->part.world) return fail(std::string(fn) + "the handle is graph-partitioned");
+  if (!h->env_mode) return fail(std::string(fn) + "the handle is not in external-action mode (call sfl_env_begin first)");
+  if (!io) return fail(std::string(fn) + "null argument");
+  if (io->capacity == 0) return fail(std::string(fn) + "capacity must be at least 1");
+  if (io->capacity > 0x7FFFFFFFu) return fail(std::string(fn) + "capacity above 2^31 - 1");
+  if (!io->env || !io->train || !io->now || !io->agent || !io->action || !io->reward || !io->next_agent ||
+      !io->next_n_actions || !io->terminal || !io->total || !io->last_count || !io->dropped)
+    return fail(std::string(fn) + "null column (only obs, next_obs and next_action_mask may be null)");
+  if (io->next_action_mask && h->max_na > SFL_MAX_ACTIONS)
+    return fail(std::string(fn) + "the map has a switch with more than SFL_MAX_ACTIONS actions (the dense action mask "
+                "cannot hold it)");
+  if (((uintptr_t)io->obs & 7u) || ((uintptr_t)io->next_obs & 7u) || ((uintptr_t)io->next_action_mask & 15u))
+    return fail(std::string(fn) + "obs and next_obs must be 8-byte and next_action_mask 16-byte aligned");
+  if (h->map.S > 0xFFFF) return fail(std::string(fn) + "more than 65,535 switches");
+  const size_t E = h->E, T = h->map.T, S = h->map.S;
+  const size_t nb = (E + TRANS_BLOCK - 1) / TRANS_BLOCK;
+  TransArgs& a = h->tr.a;
+  if (!a.tab) {
+    a.tab = h->template dalloc<TransEntry>(E * T * S);
+    a.latch = h->template dalloc<TransLatch>(E);
+    a.live = h->template dalloc<uint32_t>(E);
+    a.seen = h->template dalloc<uint32_t>(MAXW * E);
+    a.epoch = h->template dalloc<uint32_t>(E);
+    a.cnt = h->template dalloc<uint32_t>(E);
+    a.blk = h->template dalloc<uint32_t>(nb);
+    a.cur = h->template dalloc<uint64_t>(4);
+    if (!a.tab || !a.latch || !a.live || !a.seen || !a.epoch || !a.cnt || !a.blk || !a.cur) {
+      a.tab = nullptr;
+      return fail(std::string(fn) + "allocation failed");
+    }
+  }
+  a.E = h->E;
+  a.N = io->capacity;
+  a.S = h->map.S;
+  a.T = h->map.T;
+  a.K = h->map.K;
+  a.sw_np = h->map.sw_np;
+  a.sw_na = h->map.sw_na;
+  a.sw_rc = h->d_sw_rc;
+  a.st_rc = h->d_st_rc;
+  a.r_env = io->env;
+  a.r_train = io->train;
+  a.r_now = io->now;
+  a.r_agent = io->agent;
+  a.r_action = io->action;
+  a.r_reward = io->reward;
+  a.r_next_agent = io->next_agent;
+  a.r_next_na = io->next_n_actions;
+  a.r_terminal = io->terminal;
+  a.r_obs = io->obs;
+  a.r_next_obs = io->next_obs;
+  a.r_next_mask = io->next_action_mask;
+  a.total = io->total;
+  a.last_count = io->last_count;
+  a.dropped = io->dropped;
+  // an empty table (no stamp is an episode count + 1), no decision latched (agent -1), the cursor and the caller's
+  // counters at zero: memsets on the handle's stream, no wait
+  h->be.memset(a.tab, 0, E * T * S * sizeof(TransEntry));
+  h->be.memset(a.latch, 0xFF, E * sizeof(TransLatch));
+  h->be.memset(a.live, 0, E * 4);
+  h->be.memset(a.seen, 0, MAXW * E * 4);
+  h->be.memset(a.epoch, 0, E * 4);
+  h->be.memset(a.cur, 0, 4 * 8);
+  h->be.memset(a.total, 0, 8);
+  h->be.memset(a.last_count, 0, 4);
+  h->be.memset(a.dropped, 0, E * 8);
+  h->tr.parity = 0;
+  h->tr.on = true;
+  return 0;
+}
+
+template <class B>
+int trans_end(Handle<B>* h) {
+  if (!h->tr.on) return fail("sfl_env_trans_end: no transition assembler is running (sfl_env_trans_begin)");
+  h->tr.on = false;
+  return 0;
+}
+
+// behind every env step of the handle: the assembler on what this call's step read (the handle's action buffer) and
+// wrote (x: the handle's own buffers, or the caller's of sfl_env_step_dev), queued on the same stream
+template <class B>
+int trans_after_step(Handle<B>* h, const SflExt& x) {
+  if (!h->tr.on) return 0;
+  TransArgs a = h->tr.a;
+  a.parity = h->tr.parity;
+  a.actions = h->ext.actions;
+  a.agent = x.agent;
+  a.train = x.train;
+  a.slot = x.slot;
+  a.state = x.state;
+  a.mask = x.mask;
+  a.reward = x.reward;
+  a.now = x.now;
+  a.next_sw = x.next_sw;
+  a.arrived = x.arrived;
+  if (h->be.trans(a)) return fail(std::string("sfl_env_trans: ") + h->be.error());
+  h->tr.parity ^= 1u;
+  return 0;
+}
+
 // wave: sfl_env_begin_wave -- the same fresh start on the wave shape the handle was created with (EXT in sfl_wave.h)
 template <class B>
 int env_begin(Handle<B>* h, bool wave = false) {
@@ -1186,6 +1302,7 @@ int env_begin(Handle<B>* h, bool wave = false) {
   // env-major one (the memsets below do not depend on the layout), every env at reset
   h->variant = variant;
   h->env_mode = true;
+  h->tr.on = false;  // (either begin call ends a running transition assembler)
   SflState& st = h->st;
   std::vector<int32_t> ph(E, PH_RESET);
   h->be.h2d(st.phase, ph.data(), E * 4);
@@ -1229,6 +1346,7 @@ int env_step(Handle<B>* h, sfl_env_io* io) {
   float ms = 0.f;
   if (h->be.run_ext(h->map, h->st, c, h->variant, &ms)) return fail(std::string("sfl_env_step: ") + h->be.error());
   h->last_kernel_ms = ms;
+  if (int rc = trans_after_step(h, x)) return rc;
   auto get = [&](void* dst, const void* src, size_t n) {
     if (dst) h->be.d2h_async(dst, src, n);
   };
@@ -1304,7 +1422,7 @@ int env_step_dev(Handle<B>* h, const sfl_env_dev_io* dio) {
   c.launch_ticks = h->d_launch_ticks;
   c.launch_bytes = h->d_launch_bytes;
   if (h->be.run_ext_dev(h->map, h->st, c, x, enc, h->variant)) return fail(std::string("sfl_env_step_dev: ") + h->be.error());
-  return 0;
+  return trans_after_step(h, x);
 }
 
 // sfl_env_sync: wait for the handle's stream and report the envs' error flags as sfl_env_step does (the

@@ -111,6 +111,11 @@ struct HostBackend {
     *ms = 0.f;
     return 0;
   }
+  // sfl_env_trans_*: the assembler's two passes as plain loops (sfl_trans.h)
+  int trans(const sfl::TransArgs& a) {
+    sfl::trans_host(a);
+    return 0;
+  }
   int sync() { return 0; }
   uint64_t n_wait = 0;  // (nothing to wait for: the host build runs on the caller's thread)
   const uint32_t* seedseq_table() { return nullptr; }  // the host build draws every sub-generator

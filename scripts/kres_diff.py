@@ -7,7 +7,8 @@ k_wave_g_bank: sfl_bank_eval) are listed as "BANK " + the key of their Plain twi
 that twin.  The "code" column says whether the
 kernel's machine code (the symbol's bytes in its code object's .text) is the same in both, or the same but for
 pc-relative addresses (same_code).  Exit status 1 if a kernel
-present in both differs in a resource field (registers, spills, scratch, LDS); code bytes alone do not fail.
+present in both differs in a resource field (registers, spills, scratch, LDS); code bytes alone do not fail.  The
+transition assembler's kernels (k_trans_count, k_trans_write: sfl_trans.hip) are listed by name.
 Usage: python scripts/kres_diff.py OLD.so NEW.so [--md]"""
 import re
 import struct
@@ -65,6 +66,11 @@ def kernels_of(co):
         # (Itanium mangling: k_waveILi8ELi2ELb1E...E -- integer and bool template arguments only)
         m = re.search(r"\d+(k_wave_g_bank|k_wave2_bank|k_wave_bank|k_wave_g|k_wave2_part|k_wave_part|k_wave2|k_wave)I((?:L[ib]\d+E)+)E", name)
         if not m:
+            # the transition assembler's kernels (sfl_trans.hip: no template arguments), listed by name
+            t = re.search(r"\d+(k_trans_[a-z]+)", name)
+            if t:
+                vals = [int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in FIELDS]
+                out[t.group(1)] = vals + [size.get(name, -1), code.get(name)]
             continue
         args = [("true" if v == "1" else "false") if t == "b" else v for t, v in re.findall(r"L([ib])(\d+)E", m.group(2))]
         vals = [int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in FIELDS]
