@@ -22,7 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("SFL_ARCH", "gfx950")
-SOURCES = ["sfl.hip", "sfl_kwave_v7.hip", "sfl_kwave_hpg.hip", "sfl_kwave_hpg_v7.hip", "sfl_kwave_ext.hip", "sfl_kwave_bank.hip", "sfl_consensus.hip", "sfl_consensus.h", "sfl_curve.hip", "sfl_curve.h", "sfl_eval.hip", "sfl_eval.h", "sfl_snap.hip", "sfl_snap.h", "sfl_trans.hip", "sfl_trans.h", "sfl_kwave_g.h", "sfl_core.h", "sfl_wave.h", "sfl_rng.h", "sfl_engine.h", "sfl_part.h",
+SOURCES = ["sfl.hip", "sfl_kwave_v7.hip", "sfl_kwave_hpg.hip", "sfl_kwave_hpg_v7.hip", "sfl_kwave_ext.hip", "sfl_kwave_bank.hip", "sfl_consensus.hip", "sfl_consensus.h", "sfl_cells.h", "sfl_launch.h", "sfl_curve.hip", "sfl_curve.h", "sfl_eval.hip", "sfl_eval.h", "sfl_snap.hip", "sfl_snap.h", "sfl_trans.hip", "sfl_trans.h", "sfl_kwave_g.h", "sfl_core.h", "sfl_wave.h", "sfl_rng.h", "sfl_engine.h", "sfl_part.h",
            "sfl_mfgen.h", "sfl_capi.inc", "sfl_hostsim.cpp", "sfl_experiment.h", os.path.join("..", "..", "include", "sfl.h")]
 # libsfl.so's translation units and the compiler flags each adds to the common ones: variant 7 of k_wave_g (the
 # bench's c3 shape) with LLVM's register-minimising machine scheduler -- c3 +6.5 %, every other kernel loses with

@@ -611,6 +611,23 @@ struct HipBackend {
     return false;
   }
   const char* error() const { return err.c_str(); }
+
+ private:
+  // a satellite unit's failed launch (sfl_launch.h) as the handle's error
+  int fail(const sfl::LaunchErr& le) {
+    check((hipError_t)le.code, le.what);
+    return -1;
+  }
+  // the end of a timed call: ev1 behind what was queued since ev0, the wait for it (`what` names it in an error), and
+  // the time between the two events in *ms
+  int timed(const char* what, float* ms) {
+    check(hipEventRecord(ev1, stream), "event");
+    if (!check(event_wait(ev1), what)) return -1;
+    *ms = elapsed_ms();
+    return err.empty() ? 0 : -1;
+  }
+
+ public:
   int init(int device) {
     dev = device;
     int n = 0;
@@ -723,25 +740,16 @@ struct HipBackend {
       sflk::launch({variant,
                     bank ? sflk::Mode::Bank : hpg ? sflk::Mode::Hpg : c.trace ? sflk::Mode::Trace : c.phase_cyc ? sflk::Mode::Timed : sflk::Mode::Plain,
                     s.E, stream, pm, ps, pc});
-    else if (m.T <= 32) k_run<1><<<blocks, 256, 0, stream>>>(pm, ps, pc);
-    else if (m.T <= 64) k_run<2><<<blocks, 256, 0, stream>>>(pm, ps, pc);
-    else k_run<4><<<blocks, 256, 0, stream>>>(pm, ps, pc);
+    else sfl::with_nw(m.T, [&](auto nw) { k_run<decltype(nw)::value><<<blocks, 256, 0, stream>>>(pm, ps, pc); });
     if (!check(hipGetLastError(), "k_run launch")) return -1;
-    check(hipEventRecord(ev1, stream), "event");
-    if (!check(event_wait(ev1), "k_run")) return -1;
-    float t = 0.f;
-    hipEventElapsedTime(&t, ev0, ev1);
-    *ms = t;
-    return err.empty() ? 0 : -1;
+    return timed("k_run", ms);
   }
   // external-action mode's env step: the handle's wave kernel (sfl_env_begin_wave: variant > 0), else k_run_ext
   void launch_ext(int variant, const sfl::SflMap& m, uint32_t E, const sfl::SflMap* pm, const sfl::SflState* ps,
                   const sfl::SflCtl* pc) {
     const unsigned blocks = (E + 63) / 64;  // (64-thread blocks: few envs, spread over the CUs)
     if (variant >= 1 && variant < sfl::kNumVariants) sflk::launch({variant, sflk::Mode::Ext, E, stream, pm, ps, pc});
-    else if (m.T <= 32) k_run_ext<1><<<blocks, 64, 0, stream>>>(pm, ps, pc);
-    else if (m.T <= 64) k_run_ext<2><<<blocks, 64, 0, stream>>>(pm, ps, pc);
-    else k_run_ext<4><<<blocks, 64, 0, stream>>>(pm, ps, pc);
+    else sfl::with_nw(m.T, [&](auto nw) { k_run_ext<decltype(nw)::value><<<blocks, 64, 0, stream>>>(pm, ps, pc); });
   }
   // external-action mode: one call = every env applies its action and runs to its next observation
   int run_ext(const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c, int variant, float* ms) {
@@ -752,12 +760,7 @@ struct HipBackend {
     check(hipEventRecord(ev0, stream), "event");
     launch_ext(variant, m, s.E, pm, ps, pc);
     if (!check(hipGetLastError(), "k_run_ext launch")) return -1;
-    check(hipEventRecord(ev1, stream), "event");
-    if (!check(event_wait(ev1), "k_run_ext")) return -1;
-    float t = 0.f;
-    hipEventElapsedTime(&t, ev0, ev1);
-    *ms = t;
-    return err.empty() ? 0 : -1;
+    return timed("k_run_ext", ms);
   }
   // sfl_env_step_dev: k_run_ext writing the caller's device buffers (x), then k_env_encode, queued without a
   // wait.  The parameter block SflMap | SflState | SflCtl | SflExt has a device copy of its own, uploaded only
@@ -788,29 +791,14 @@ struct HipBackend {
   static constexpr bool kConsPartials = true;
   int consensus(const sfl::ConsArgs& a, float* ms) {
     check(hipEventRecord(ev0, stream), "event");
-    const char* what = "";
-    int code = 0;
-    if (sfl::consensus_launch(a, (void*)stream, &what, &code)) {
-      if (err.empty()) err = std::string(what) + ": " + hipGetErrorString((hipError_t)code);
-      return -1;
-    }
-    check(hipEventRecord(ev1, stream), "event");
-    if (!check(event_wait(ev1), "sfl_consensus kernels")) return -1;
-    float t = 0.f;
-    hipEventElapsedTime(&t, ev0, ev1);
-    *ms = t;
-    return err.empty() ? 0 : -1;
+    if (sfl::LaunchErr le = sfl::consensus_launch(a, (void*)stream)) return fail(le);
+    return timed("sfl_consensus kernels", ms);
   }
   // sfl_curve_*: k_curve_fold of sfl_curve.hip queued on the handle's stream between the two events (elapsed_ms()
   // after the caller's sync is the fold's time), or k_curve_reset
   int curve(const sfl::CurveArgs& a, bool reset) {
     if (!reset) check(hipEventRecord(ev0, stream), "event");
-    const char* what = "";
-    int code = 0;
-    if (sfl::curve_launch(a, reset, (void*)stream, &what, &code)) {
-      if (err.empty()) err = std::string(what) + ": " + hipGetErrorString((hipError_t)code);
-      return -1;
-    }
+    if (sfl::LaunchErr le = sfl::curve_launch(a, reset, (void*)stream)) return fail(le);
     if (!reset) check(hipEventRecord(ev1, stream), "event");
     return err.empty() ? 0 : -1;
   }
@@ -819,12 +807,7 @@ struct HipBackend {
   // that empties the exploit cells
   int curve_exploit(const sfl::CurveXArgs& a, bool reset) {
     if (!ev2 && !check(hipEventCreate(&ev2), "hipEventCreate")) return -1;
-    const char* what = "";
-    int code = 0;
-    if (sfl::curve_xlaunch(a, reset, (void*)stream, &what, &code)) {
-      if (err.empty()) err = std::string(what) + ": " + hipGetErrorString((hipError_t)code);
-      return -1;
-    }
+    if (sfl::LaunchErr le = sfl::curve_xlaunch(a, reset, (void*)stream)) return fail(le);
     if (!reset) check(hipEventRecord(ev2, stream), "event");
     return err.empty() ? 0 : -1;
   }
@@ -837,39 +820,19 @@ struct HipBackend {
   // after the caller's sync is the fold's time)
   int eval_fold(const sfl::EvalArgs& a) {
     check(hipEventRecord(ev0, stream), "event");
-    const char* what = "";
-    int code = 0;
-    if (sfl::eval_launch(a, (void*)stream, &what, &code)) {
-      if (err.empty()) err = std::string(what) + ": " + hipGetErrorString((hipError_t)code);
-      return -1;
-    }
+    if (sfl::LaunchErr le = sfl::eval_launch(a, (void*)stream)) return fail(le);
     check(hipEventRecord(ev1, stream), "event");
     return err.empty() ? 0 : -1;
   }
   // sfl_state_*: one phase's kernels of sfl_snap.hip on the handle's stream, timed between the two events
   int snap(const sfl::SnapArgs& a, int phase, float* ms) {
     check(hipEventRecord(ev0, stream), "event");
-    const char* what = "";
-    int code = 0;
-    if (sfl::snap_launch(a, phase, (void*)stream, &what, &code)) {
-      if (err.empty()) err = std::string(what) + ": " + hipGetErrorString((hipError_t)code);
-      return -1;
-    }
-    check(hipEventRecord(ev1, stream), "event");
-    if (!check(event_wait(ev1), "sfl_state kernels")) return -1;
-    float t = 0.f;
-    hipEventElapsedTime(&t, ev0, ev1);
-    *ms = t;
-    return err.empty() ? 0 : -1;
+    if (sfl::LaunchErr le = sfl::snap_launch(a, phase, (void*)stream)) return fail(le);
+    return timed("sfl_state kernels", ms);
   }
   // sfl_env_trans_*: the two kernels of sfl_trans.hip queued behind the env step, without a wait
   int trans(const sfl::TransArgs& a) {
-    const char* what = "";
-    int code = 0;
-    if (sfl::trans_launch(a, (void*)stream, &what, &code)) {
-      if (err.empty()) err = std::string(what) + ": " + hipGetErrorString((hipError_t)code);
-      return -1;
-    }
+    if (sfl::LaunchErr le = sfl::trans_launch(a, (void*)stream)) return fail(le);
     return err.empty() ? 0 : -1;
   }
   int sync() { return check(stream_wait(), "sync") && err.empty() ? 0 : -1; }
@@ -943,11 +906,8 @@ struct HipBackend {
     // one wave per block: a round's envs spread over as many CUs as possible
     const unsigned blocks = (s.E + 63) / 64;
     // the wave kernel of the handle's row (the G == 64 rows), else the lane-per-env body
-    if (launch_part_wave(std::make_integer_sequence<int, sfl::kNumVariants - 1>{}, variant, s.E, stream, &pp->m, &pp->s, &pp->c, &pp->t))
-      ;
-    else if (m.T <= 32) k_part_local<1><<<blocks, 64, 0, stream>>>(&pp->m, &pp->s, &pp->c, &pp->t);
-    else if (m.T <= 64) k_part_local<2><<<blocks, 64, 0, stream>>>(&pp->m, &pp->s, &pp->c, &pp->t);
-    else k_part_local<4><<<blocks, 64, 0, stream>>>(&pp->m, &pp->s, &pp->c, &pp->t);
+    if (!launch_part_wave(std::make_integer_sequence<int, sfl::kNumVariants - 1>{}, variant, s.E, stream, &pp->m, &pp->s, &pp->c, &pp->t))
+      sfl::with_nw(m.T, [&](auto nw) { k_part_local<decltype(nw)::value><<<blocks, 64, 0, stream>>>(&pp->m, &pp->s, &pp->c, &pp->t); });
     if (!check(hipGetLastError(), "k_part_local")) return -1;
     // (256 envs per block: fewer blocks reserve places and count themselves done; 64 measured -1.3 %)
     k_part_compact<<<(s.E + SFL_COMPACT_BLOCK - 1) / SFL_COMPACT_BLOCK, SFL_COMPACT_BLOCK, 0, stream>>>(&pp->t, &pp->s, &pp->c,

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/sfl.h"
+#include "sfl_launch.h"
 
 namespace sfl {
 
@@ -125,9 +126,9 @@ inline void consensus_host(const ConsArgs& a) {
   }
 }
 
-// sfl_consensus.hip: queues the kernels of one call on `stream` (a hipStream_t); 0, or -1 with the failing launch's
-// name in *what and HIP's error code in *code
-int consensus_launch(const ConsArgs& a, void* stream, const char** what, int* code);
+// sfl_consensus.hip: queues the kernels of one call on `stream` (a hipStream_t); the failing launch, if any
+// (sfl_launch.h)
+LaunchErr consensus_launch(const ConsArgs& a, void* stream);
 constexpr uint32_t CONS_TILE = 512;  // cells per block of the kernels (cells_cap is a multiple of it)
 
 }  // namespace sfl

@@ -234,13 +234,8 @@ __global__ void __launch_bounds__(CONS_BLOCK) k_cons_share_keys(ConsArgs a, uint
 
 namespace sfl {
 
-int consensus_launch(const ConsArgs& a, void* stream_, const char** what, int* code) {
+LaunchErr consensus_launch(const ConsArgs& a, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  auto bad = [&](const char* w, hipError_t rc) {
-    *what = w;
-    *code = (int)rc;
-    return -1;
-  };
   const uint64_t kMaxGrid = 0x7FFFFFFFull;
   const uint32_t wtiles = (a.tw + CONS_BLOCK - 1) / CONS_BLOCK;
   const uint64_t all_tiles = (a.Q + CONS_TILE - 1) / CONS_TILE;
@@ -248,11 +243,11 @@ int consensus_launch(const ConsArgs& a, void* stream_, const char** what, int* c
   // (a lane of the two-cell kernels covers CONS_TILE / CONS_BLOCK = 2 cells; the one-cell kernels take two blocks per tile)
   const uint32_t per = v2 ? 1u : CONS_TILE / CONS_BLOCK;
   if ((uint64_t)a.n_jobs * all_tiles * per > kMaxGrid || (uint64_t)a.n_jobs * wtiles > kMaxGrid)
-    return bad("sfl_consensus: more than 2^31 blocks (jobs x cell tiles)", hipErrorInvalidConfiguration);
+    return launch_err("sfl_consensus: more than 2^31 blocks (jobs x cell tiles)", hipErrorInvalidConfiguration);
   hipLaunchKernelGGL(k_cons_keys, dim3(a.n_jobs * wtiles), dim3(CONS_BLOCK), 0, stream, a, wtiles);
   if (a.n_combos)
     hipLaunchKernelGGL(k_cons_keys_combine, dim3(a.n_combos * wtiles), dim3(CONS_BLOCK), 0, stream, a, wtiles);
-  if (hipError_t rc = hipGetLastError()) return bad("k_cons_keys", rc);
+  if (LaunchErr e = launch_err("k_cons_keys")) return e;
   // (cells_cap covers the table: one pass; a smaller cells_cap would reduce it a range of cells at a time)
   const uint64_t step = a.cells_cap;
   for (uint64_t c0 = 0; c0 < a.Q; c0 += step) {
@@ -266,11 +261,11 @@ int consensus_launch(const ConsArgs& a, void* stream_, const char** what, int* c
       if (mx) hipLaunchKernelGGL((k_cons_reduce<SFL_CONSENSUS_MAX, 1>), grid, dim3(CONS_BLOCK), 0, stream, a, c0, tiles * per);
       else hipLaunchKernelGGL((k_cons_reduce<SFL_CONSENSUS_MEAN, 1>), grid, dim3(CONS_BLOCK), 0, stream, a, c0, tiles * per);
     }
-    if (hipError_t rc = hipGetLastError()) return bad("k_cons_reduce", rc);
+    if (LaunchErr e = launch_err("k_cons_reduce")) return e;
     if (a.n_combos) {
       if (mx) hipLaunchKernelGGL(k_cons_combine<SFL_CONSENSUS_MAX>, dim3(a.n_combos * tiles), dim3(CONS_BLOCK), 0, stream, a, c0, tiles);
       else hipLaunchKernelGGL(k_cons_combine<SFL_CONSENSUS_MEAN>, dim3(a.n_combos * tiles), dim3(CONS_BLOCK), 0, stream, a, c0, tiles);
-      if (hipError_t rc = hipGetLastError()) return bad("k_cons_combine", rc);
+      if (LaunchErr e = launch_err("k_cons_combine")) return e;
     }
   }
   if (a.flags & SFL_CONSENSUS_SHARE) {
@@ -278,9 +273,9 @@ int consensus_launch(const ConsArgs& a, void* stream_, const char** what, int* c
     if (v2) hipLaunchKernelGGL(k_cons_share<2>, dim3(a.n_jobs * tiles), dim3(CONS_BLOCK), 0, stream, a, tiles);
     else hipLaunchKernelGGL(k_cons_share<1>, dim3(a.n_jobs * tiles), dim3(CONS_BLOCK), 0, stream, a, tiles);
     hipLaunchKernelGGL(k_cons_share_keys, dim3(a.n_jobs * wtiles), dim3(CONS_BLOCK), 0, stream, a, wtiles);
-    if (hipError_t rc = hipGetLastError()) return bad("k_cons_share", rc);
+    if (LaunchErr e = launch_err("k_cons_share")) return e;
   }
-  return 0;
+  return {};
 }
 
 }  // namespace sfl

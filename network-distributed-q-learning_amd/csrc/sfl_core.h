@@ -19,6 +19,9 @@
 // offsets.
 #pragma once
 #include <stdint.h>
+
+#include <type_traits>
+
 #include "sfl_rng.h"
 
 #if !defined(__HIPCC__)
@@ -1292,6 +1295,15 @@ SFL_FN bool wave_any(bool pred) {
 // ---------------------------------------------------------------------------
 // driver: one env until its episode target / decision budget
 // ---------------------------------------------------------------------------
+// The lane-per-env bodies' NW (train bitmask words held in registers) for a map of T trains, chosen on the host:
+// f(std::integral_constant<int, NW>) with the smallest of 1, 2, 4 that has T <= 32 * NW.
+template <class F>
+inline void with_nw(int32_t T, F&& f) {
+  if (T <= 32) f(std::integral_constant<int, 1>{});
+  else if (T <= 64) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 4>{});
+}
+
 template <int NW>
 SFL_FN void env_run(const SflMap& m, const SflState& s, const SflCtl& c, uint32_t e) {
   using V = Env<NW>;

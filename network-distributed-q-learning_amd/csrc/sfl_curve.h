@@ -1,11 +1,14 @@
-// Step-mode learning curves (include/sfl.h sfl_curve_*): the cell layout, the work description both backends take, and
-// the host build's plain loops.  The rule is stated once, in include/sfl.h and DESIGN.md §17; curve_fold_host below, the
-// kernel of sfl_curve.hip and the test model (tests/_curve.py) are three implementations of it that agree exactly.
+// Step-mode learning curves (include/sfl.h sfl_curve_*): the cell layouts (sfl_cells.h), the work description both
+// backends take, the one function that builds an episode's (a round's) contribution, and the host build's plain loops.
+// The rule is stated once, in include/sfl.h and DESIGN.md §17; curve_fold_host below, the kernel of sfl_curve.hip and
+// the test model (tests/_curve.py) are three implementations of it that agree exactly.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/sfl.h"
+#include "sfl_cells.h"
+#include "sfl_launch.h"
 
 namespace sfl {
 
@@ -32,58 +35,65 @@ struct CurveArgs {
   int64_t* cells;               // [n_bins][n_series][CV_WORDS]
 };
 
-#if defined(__HIPCC__)
-#define SFL_CV_FN __host__ __device__ inline
-#else
-#define SFL_CV_FN inline
-#endif
-
-SFL_CV_FN size_t curve_cell_of(const CurveArgs& a, int32_t episode, uint32_t series) {
+SFL_CELL_FN size_t curve_cell_of(const CurveArgs& a, int32_t episode, uint32_t series) {
   int32_t bin = episode / a.bin_episodes;
   if (bin > a.n_bins - 1) bin = a.n_bins - 1;
   return (size_t)bin * a.n_series + series;
 }
 
-SFL_CV_FN void curve_cell_clear(int64_t* c) {
-  for (int k = 0; k < CV_WORDS; ++k) c[k] = 0;
-  c[CV_ARR_MIN] = c[CV_REW_MIN] = c[CV_EP_FIRST] = INT64_MAX;
-  c[CV_ARR_MAX] = c[CV_REW_MAX] = INT64_MIN;
-  c[CV_EP_LAST] = -1;
+// the curve's layout (sfl_cells.h): each word's reduction and what an empty cell holds there
+struct EpisodeCell {
+  static constexpr int N = CV_WORDS, COUNT = CV_COUNT;
+  SFL_CELL_FN static constexpr int op(int k) {
+    return (k == CV_ARR_MIN || k == CV_REW_MIN || k == CV_EP_FIRST) ? OP_MIN
+           : (k == CV_ARR_MAX || k == CV_REW_MAX || k == CV_EP_LAST) ? OP_MAX
+                                                                     : OP_SUM;
+  }
+  // (an empty cell's ep_last reads -1 through sfl_curve_read)
+  SFL_CELL_FN static constexpr int64_t identity(int k) { return k == CV_EP_LAST ? -1 : cell_op_identity(op(k)); }
+};
+
+// episode i of env e (of series `series`) as a cell of one episode in v; returns the cell it belongs to.  An episode
+// below `kept` was overwritten in the ring: it counts as lost and nothing else
+SFL_CELL_FN void curve_episode_cell(const CurveArgs& a, uint32_t e, uint32_t series, int32_t i, int32_t kept, int64_t* v,
+                                    uint32_t& key) {
+  const size_t E = a.E;
+  key = (uint32_t)curve_cell_of(a, i, series);
+  cell_clear<EpisodeCell>(v);
+  if (i < kept) {
+    v[CV_LOST] = 1;
+  } else {
+    const size_t row = (size_t)(i % a.ring_cap);
+    const int64_t arrived = a.st_arrived[row * E + e], reward = (int64_t)a.st_cum[row * E + e];
+    const int64_t dec = a.st_dec[row * E + e];
+    int64_t delay = 0;
+    for (int32_t h = 0; h < a.T; ++h) delay += a.st_delays[(row * (size_t)a.T + h) * E + e];
+    v[CV_COUNT] = 1;
+    v[CV_ARR_SUM] = v[CV_ARR_MIN] = v[CV_ARR_MAX] = arrived;
+    v[CV_ALL_ARR] = arrived == a.T ? 1 : 0;
+    v[CV_REW_SUM] = v[CV_REW_MIN] = v[CV_REW_MAX] = reward;
+    v[CV_DEC_SUM] = dec;
+    v[CV_TICK_SUM] = a.st_ticks[row * E + e];
+    v[CV_MF_SUM] = a.st_mf[row * E + e];
+    v[CV_DELAY_SUM] = delay;
+    v[CV_TRUNC] = dec > a.max_steps ? 1 : 0;
+    v[CV_EP_FIRST] = v[CV_EP_LAST] = i;
+  }
 }
 
-// The host build: the rule as written, one env, one episode at a time ("device" memory is host memory here).
-inline void curve_reset_host(const CurveArgs& a) {
-  for (size_t c = 0; c < (size_t)a.n_bins * a.n_series; ++c) curve_cell_clear(a.cells + c * CV_WORDS);
-}
+// The host build: the rule as written -- in env order, one contribution at a time, no wave logic ("device" memory is
+// host memory here).
+inline void curve_reset_host(const CurveArgs& a) { cells_reset_host<EpisodeCell>(a.cells, (size_t)a.n_bins * a.n_series); }
 
 inline void curve_fold_host(const CurveArgs& a) {
-  const size_t E = a.E;
   for (uint32_t e = 0; e < a.E; ++e) {
     const int32_t end = a.ep_t[e], b = a.mark[e];
     const int32_t kept = end - a.ring_cap > b ? end - a.ring_cap : b;
-    for (int32_t i = b; i < kept; ++i) a.cells[curve_cell_of(a, i, a.series[e]) * CV_WORDS + CV_LOST] += 1;
-    for (int32_t i = kept; i < end; ++i) {
-      int64_t* c = a.cells + curve_cell_of(a, i, a.series[e]) * CV_WORDS;
-      const size_t row = (size_t)(i % a.ring_cap);
-      const int64_t arrived = a.st_arrived[row * E + e], reward = (int64_t)a.st_cum[row * E + e];
-      const int64_t dec = a.st_dec[row * E + e];
-      int64_t delay = 0;
-      for (int32_t h = 0; h < a.T; ++h) delay += a.st_delays[(row * (size_t)a.T + h) * E + e];
-      c[CV_COUNT] += 1;
-      c[CV_ARR_SUM] += arrived;
-      if (arrived < c[CV_ARR_MIN]) c[CV_ARR_MIN] = arrived;
-      if (arrived > c[CV_ARR_MAX]) c[CV_ARR_MAX] = arrived;
-      c[CV_ALL_ARR] += arrived == a.T ? 1 : 0;
-      c[CV_REW_SUM] += reward;
-      if (reward < c[CV_REW_MIN]) c[CV_REW_MIN] = reward;
-      if (reward > c[CV_REW_MAX]) c[CV_REW_MAX] = reward;
-      c[CV_DEC_SUM] += dec;
-      c[CV_TICK_SUM] += a.st_ticks[row * E + e];
-      c[CV_MF_SUM] += a.st_mf[row * E + e];
-      c[CV_DELAY_SUM] += delay;
-      c[CV_TRUNC] += dec > a.max_steps ? 1 : 0;
-      if (i < c[CV_EP_FIRST]) c[CV_EP_FIRST] = i;
-      if (i > c[CV_EP_LAST]) c[CV_EP_LAST] = i;
+    for (int32_t i = b; i < end; ++i) {
+      int64_t v[CV_WORDS];
+      uint32_t key;
+      curve_episode_cell(a, e, a.series[e], i, kept, v, key);
+      cell_merge<EpisodeCell>(a.cells + (size_t)key * CV_WORDS, v);
     }
     a.mark[e] = end;
   }
@@ -114,63 +124,74 @@ struct CurveXArgs {
 };
 
 // the rounds an env at episode index a with flags word `flags` has completed under frequency f
-SFL_CV_FN int32_t curve_rounds_done(int32_t a, uint32_t flags, int32_t f) {
+SFL_CELL_FN int32_t curve_rounds_done(int32_t a, uint32_t flags, int32_t f) {
   return a / f + (((flags & CVX_DONE) && (a + 1) % f == 0) ? 1 : 0);
 }
 
 // the episode round r precedes (never above the env's episode index, so it fits an int32)
-SFL_CV_FN int32_t curve_round_episode(int32_t r, int32_t f) { return (int32_t)(((int64_t)r + 1) * f - 1); }
+SFL_CELL_FN int32_t curve_round_episode(int32_t r, int32_t f) { return (int32_t)(((int64_t)r + 1) * f - 1); }
 
-SFL_CV_FN size_t curve_xcell_of(const CurveXArgs& a, int32_t episode, uint32_t series) {
+SFL_CELL_FN size_t curve_xcell_of(const CurveXArgs& a, int32_t episode, uint32_t series) {
   int32_t bin = episode / a.bin_episodes;
   if (bin > a.n_bins - 1) bin = a.n_bins - 1;
   return (size_t)bin * a.n_series + series;
 }
 
-SFL_CV_FN void curve_xcell_clear(int64_t* c) {
-  for (int k = 0; k < XV_WORDS; ++k) c[k] = 0;
-  c[XV_ARR_MIN] = c[XV_REW_MIN] = c[XV_EP_FIRST] = INT64_MAX;
-  c[XV_ARR_MAX] = c[XV_REW_MAX] = INT64_MIN;
-  c[XV_EP_LAST] = -1;
+struct ExploitCell {
+  static constexpr int N = XV_WORDS, COUNT = XV_COUNT;
+  SFL_CELL_FN static constexpr int op(int k) {
+    return (k == XV_ARR_MIN || k == XV_REW_MIN || k == XV_EP_FIRST) ? OP_MIN
+           : (k == XV_ARR_MAX || k == XV_REW_MAX || k == XV_EP_LAST) ? OP_MAX
+                                                                     : OP_SUM;
+  }
+  // (an empty cell's ep_last reads -1 through sfl_curve_read_exploit)
+  SFL_CELL_FN static constexpr int64_t identity(int k) { return k == XV_EP_LAST ? -1 : cell_op_identity(op(k)); }
+};
+
+// greedy round r of env e (of series `series`) as a cell of one round in v; returns the cell it belongs to (by the
+// episode the round precedes).  A round below `kept` was overwritten in the ring: it counts as lost and nothing else
+SFL_CELL_FN void curve_round_cell(const CurveXArgs& a, uint32_t e, uint32_t series, int32_t r, int32_t kept, int64_t* v,
+                                  uint32_t& key) {
+  const size_t E = a.E;
+  const int32_t t = curve_round_episode(r, a.f);
+  key = (uint32_t)curve_xcell_of(a, t, series);
+  cell_clear<ExploitCell>(v);
+  if (r < kept) {
+    v[XV_LOST] = 1;
+  } else {
+    const size_t row = (size_t)(t % a.ring_cap);
+    const int64_t arrived = a.sx_arrived[row * E + e], reward = (int64_t)a.sx_cum[row * E + e];
+    v[XV_COUNT] = 1;
+    v[XV_ARR_SUM] = v[XV_ARR_MIN] = v[XV_ARR_MAX] = arrived;
+    v[XV_ALL_ARR] = arrived == a.T ? 1 : 0;
+    v[XV_REW_SUM] = v[XV_REW_MIN] = v[XV_REW_MAX] = reward;
+    v[XV_EP_FIRST] = v[XV_EP_LAST] = t;
+  }
 }
 
-inline void curve_xreset_host(const CurveXArgs& a) {
-  for (size_t c = 0; c < (size_t)a.n_bins * a.n_series; ++c) curve_xcell_clear(a.cells + c * XV_WORDS);
-}
+// the host build, as curve_fold_host: in env order, one contribution at a time, no wave logic
+inline void curve_xreset_host(const CurveXArgs& a) { cells_reset_host<ExploitCell>(a.cells, (size_t)a.n_bins * a.n_series); }
 
 inline void curve_xfold_host(const CurveXArgs& a) {
-  const size_t E = a.E;
   for (uint32_t e = 0; e < a.E; ++e) {
     int32_t n = curve_rounds_done(a.ep_t[e], a.eflags[e], a.f);
     if (a.limit && a.limit[e] < n) n = a.limit[e];
     const int32_t b = a.mark[e];
     const int32_t kept = n - a.period > b ? n - a.period : b;
-    for (int32_t r = b; r < kept; ++r)
-      a.cells[curve_xcell_of(a, curve_round_episode(r, a.f), a.series[e]) * XV_WORDS + XV_LOST] += 1;
-    for (int32_t r = kept; r < n; ++r) {
-      const int32_t t = curve_round_episode(r, a.f);
-      int64_t* c = a.cells + curve_xcell_of(a, t, a.series[e]) * XV_WORDS;
-      const size_t row = (size_t)(t % a.ring_cap);
-      const int64_t arrived = a.sx_arrived[row * E + e], reward = (int64_t)a.sx_cum[row * E + e];
-      c[XV_COUNT] += 1;
-      c[XV_ARR_SUM] += arrived;
-      if (arrived < c[XV_ARR_MIN]) c[XV_ARR_MIN] = arrived;
-      if (arrived > c[XV_ARR_MAX]) c[XV_ARR_MAX] = arrived;
-      c[XV_ALL_ARR] += arrived == a.T ? 1 : 0;
-      c[XV_REW_SUM] += reward;
-      if (reward < c[XV_REW_MIN]) c[XV_REW_MIN] = reward;
-      if (reward > c[XV_REW_MAX]) c[XV_REW_MAX] = reward;
-      if (t < c[XV_EP_FIRST]) c[XV_EP_FIRST] = t;
-      if (t > c[XV_EP_LAST]) c[XV_EP_LAST] = t;
+    for (int32_t r = b; r < n; ++r) {
+      int64_t v[XV_WORDS];
+      uint32_t key;
+      curve_round_cell(a, e, a.series[e], r, kept, v, key);
+      cell_merge<ExploitCell>(a.cells + (size_t)key * XV_WORDS, v);
     }
     a.mark[e] = n;
   }
 }
 
 // sfl_curve.hip: queues one kernel on `stream` (a hipStream_t) -- the fold, or with `reset` the kernel that empties the
-// cells; 0, or -1 with the failing launch's name in *what and HIP's error code in *code
-int curve_launch(const CurveArgs& a, bool reset, void* stream, const char** what, int* code);
+// cells; the failing launch, if any (sfl_launch.h)
+LaunchErr curve_launch(const CurveArgs& a, bool reset, void* stream);
 // the same for the exploit record: k_curve_fold_exploit, or with `reset` the kernel that empties its cells
-int curve_xlaunch(const CurveXArgs& a, bool reset, void* stream, const char** what, int* code);
+LaunchErr curve_xlaunch(const CurveXArgs& a, bool reset, void* stream);
 
 }  // namespace sfl

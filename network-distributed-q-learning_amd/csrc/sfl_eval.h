@@ -7,6 +7,8 @@
 #include <stdint.h>
 
 #include "../../include/sfl.h"
+#include "sfl_cells.h"
+#include "sfl_launch.h"
 
 namespace sfl {
 
@@ -32,24 +34,21 @@ struct EvalArgs {
   int64_t* cells;              // [n_policies][EV_WORDS]
 };
 
-#if defined(__HIPCC__)
-#define SFL_EV_FN __host__ __device__ inline
-#else
-#define SFL_EV_FN inline
-#endif
-
-SFL_EV_FN void eval_cell_clear(int64_t* c) {
-  for (int k = 0; k < EV_WORDS; ++k) c[k] = 0;
-  c[EV_ARR_MIN] = c[EV_REW_MIN] = INT64_MAX;
-  c[EV_ARR_MAX] = c[EV_REW_MAX] = INT64_MIN;
-}
+// the per-policy cell's layout (sfl_cells.h): each word's reduction and what an empty cell holds there
+struct EvalCell {
+  static constexpr int N = EV_WORDS, COUNT = EV_EPISODES;  // (a contribution is one episode: COUNT is 1 in each)
+  SFL_CELL_FN static constexpr int op(int k) {
+    return (k == EV_ARR_MIN || k == EV_REW_MIN) ? OP_MIN : (k == EV_ARR_MAX || k == EV_REW_MAX) ? OP_MAX : OP_SUM;
+  }
+  SFL_CELL_FN static constexpr int64_t identity(int k) { return cell_op_identity(op(k)); }
+};
 
 // env e's episode as a cell of one episode.  The per-train rule is plot.ipynb cell 15's (scripts/eval_table.py
 // classify), by train handle: arrived with delay <= 0 is early, arrived with delay > 0 late, anything else not
 // arrived -- whose delay is not counted
-SFL_EV_FN void eval_env_cell(const EvalArgs& a, uint32_t e, int64_t* v) {
+SFL_CELL_FN void eval_env_cell(const EvalArgs& a, uint32_t e, int64_t* v) {
   const size_t E = a.E;
-  eval_cell_clear(v);
+  cell_clear<EvalCell>(v);
   int64_t early = 0, late = 0, dsum = 0;
   for (int32_t h = 0; h < a.T; ++h) {
     const int64_t d = a.delays[(size_t)h * E + e];
@@ -73,23 +72,19 @@ SFL_EV_FN void eval_env_cell(const EvalArgs& a, uint32_t e, int64_t* v) {
   v[EV_TRUNC] = a.trunc[e] ? 1 : 0;
 }
 
-// The host build: the cells emptied, then one env at a time ("device" memory is host memory here).
+// The host build: the cells emptied, then in env order, one contribution at a time, no wave logic ("device" memory is
+// host memory here).
 inline void eval_fold_host(const EvalArgs& a) {
-  for (uint32_t p = 0; p < a.n_policies; ++p) eval_cell_clear(a.cells + (size_t)p * EV_WORDS);
+  cells_reset_host<EvalCell>(a.cells, a.n_policies);
   for (uint32_t e = 0; e < a.E; ++e) {
     int64_t v[EV_WORDS];
     eval_env_cell(a, e, v);
-    int64_t* c = a.cells + (size_t)a.policy[e] * EV_WORDS;
-    for (int k = 0; k < EV_WORDS; ++k) {
-      if (k == EV_ARR_MIN || k == EV_REW_MIN) c[k] = v[k] < c[k] ? v[k] : c[k];
-      else if (k == EV_ARR_MAX || k == EV_REW_MAX) c[k] = v[k] > c[k] ? v[k] : c[k];
-      else c[k] += v[k];
-    }
+    cell_merge<EvalCell>(a.cells + (size_t)a.policy[e] * EV_WORDS, v);
   }
 }
 
-// sfl_eval.hip: queues the kernel that empties the cells and k_eval_fold behind it on `stream` (a hipStream_t); 0, or
-// -1 with the failing launch's name in *what and HIP's error code in *code
-int eval_launch(const EvalArgs& a, void* stream, const char** what, int* code);
+// sfl_eval.hip: queues the kernel that empties the cells and k_eval_fold behind it on `stream` (a hipStream_t); the
+// failing launch, if any (sfl_launch.h)
+LaunchErr eval_launch(const EvalArgs& a, void* stream);
 
 }  // namespace sfl

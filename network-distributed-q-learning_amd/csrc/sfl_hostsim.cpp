@@ -49,22 +49,18 @@ struct HostBackend {
       }
   }
   int run(const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c, int /*variant*/, float* ms) {
+    sfl::with_nw(m.T, [&](auto nw) {
 #pragma omp parallel for schedule(dynamic, 1)
-    for (int64_t e = 0; e < (int64_t)s.E; ++e) {
-      if (m.T <= 32) sfl::env_run<1>(m, s, c, (uint32_t)e);
-      else if (m.T <= 64) sfl::env_run<2>(m, s, c, (uint32_t)e);
-      else sfl::env_run<4>(m, s, c, (uint32_t)e);
-    }
+      for (int64_t e = 0; e < (int64_t)s.E; ++e) sfl::env_run<decltype(nw)::value>(m, s, c, (uint32_t)e);
+    });
     *ms = 0.f;
     return 0;
   }
   int run_ext(const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c, int /*variant*/, float* ms) {
+    sfl::with_nw(m.T, [&](auto nw) {
 #pragma omp parallel for schedule(dynamic, 1)
-    for (int64_t e = 0; e < (int64_t)s.E; ++e) {
-      if (m.T <= 32) sfl::env_run_ext<1>(m, s, c, (uint32_t)e);
-      else if (m.T <= 64) sfl::env_run_ext<2>(m, s, c, (uint32_t)e);
-      else sfl::env_run_ext<4>(m, s, c, (uint32_t)e);
-    }
+      for (int64_t e = 0; e < (int64_t)s.E; ++e) sfl::env_run_ext<decltype(nw)::value>(m, s, c, (uint32_t)e);
+    });
     *ms = 0.f;
     return 0;
   }
@@ -134,12 +130,10 @@ struct HostBackend {
   }
   int part_local(const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c, const sfl::SflPart& P, int /*variant*/,
                  float* ms) {
+    sfl::with_nw(m.T, [&](auto nw) {
 #pragma omp parallel for schedule(dynamic, 1)
-    for (int64_t e = 0; e < (int64_t)s.E; ++e) {
-      if (m.T <= 32) sfl::env_run_part<1>(m, s, c, P, (uint32_t)e);
-      else if (m.T <= 64) sfl::env_run_part<2>(m, s, c, P, (uint32_t)e);
-      else sfl::env_run_part<4>(m, s, c, P, (uint32_t)e);
-    }
+      for (int64_t e = 0; e < (int64_t)s.E; ++e) sfl::env_run_part<decltype(nw)::value>(m, s, c, P, (uint32_t)e);
+    });
     part_compact(P, s, c);
     *ms = 0.f;
     return 0;

@@ -9,6 +9,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "sfl_launch.h"
+
 namespace sfl {
 
 // One SflState array as the capture sees it: `count` elements of `elem` bytes per env, env-minor (element i of env e at
@@ -106,8 +108,8 @@ inline void snap_host(const SnapArgs& a, int phase) {
   }
 }
 
-// sfl_snap.hip: queues the kernels of one phase on `stream` (a hipStream_t); 0, or -1 with the failing launch's name
-// in *what and HIP's error code in *code
-int snap_launch(const SnapArgs& a, int phase, void* stream, const char** what, int* code);
+// sfl_snap.hip: queues the kernels of one phase on `stream` (a hipStream_t); the failing launch, if any
+// (sfl_launch.h)
+LaunchErr snap_launch(const SnapArgs& a, int phase, void* stream);
 
 }  // namespace sfl

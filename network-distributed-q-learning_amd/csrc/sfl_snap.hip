@@ -185,19 +185,14 @@ __global__ void __launch_bounds__(SNAP_BLOCK) k_snap_field(SnapField f, const ui
 
 namespace sfl {
 
-int snap_launch(const SnapArgs& a, int phase, void* stream_, const char** what, int* code) {
+LaunchErr snap_launch(const SnapArgs& a, int phase, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  auto bad = [&](const char* w, hipError_t rc) {
-    *what = w;
-    *code = (int)rc;
-    return -1;
-  };
-  if (a.n == 0) return 0;
+  if (a.n == 0) return {};
   const uint64_t kMaxGrid = 0x7FFFFFFFull;
   const uint32_t rblocks = (a.rows + SNAP_BLOCK - 1) / SNAP_BLOCK;
   const uint32_t qblocks = (uint32_t)((a.Q + SNAP_BLOCK - 1) / SNAP_BLOCK);
   if ((uint64_t)a.n * rblocks > kMaxGrid || (uint64_t)a.n * qblocks > kMaxGrid)
-    return bad("sfl_state: more than 2^31 blocks (envs x row tiles)", hipErrorInvalidConfiguration);
+    return launch_err("sfl_state: more than 2^31 blocks (envs x row tiles)", hipErrorInvalidConfiguration);
   const dim3 blk(SNAP_BLOCK);
   auto fields = [&](bool gather) -> hipError_t {
     SnapField keys{a.touched, 4u, a.tw, 1u, 0u};
@@ -217,28 +212,25 @@ int snap_launch(const SnapArgs& a, int phase, void* stream_, const char** what, 
   };
   if (phase == SNAP_COUNT) {
     if (rblocks) hipLaunchKernelGGL(k_snap_live<true>, dim3(a.n * rblocks), blk, 0, stream, a, rblocks);
-    if (hipError_t rc = hipGetLastError()) return bad("k_snap_live", rc);
+    if (LaunchErr e = launch_err("k_snap_live")) return e;
     hipLaunchKernelGGL(k_snap_scan_env, dim3(a.n), blk, 0, stream, a, true);
     hipLaunchKernelGGL(k_snap_scan_all, dim3(1), blk, 0, stream, a);
-    if (hipError_t rc = hipGetLastError()) return bad("k_snap_scan", rc);
-    return 0;
+    return launch_err("k_snap_scan");
   }
   if (phase == SNAP_GATHER) {
     if (rblocks) hipLaunchKernelGGL(k_snap_rows<true>, dim3(a.n * rblocks), blk, 0, stream, a, rblocks);
-    if (hipError_t rc = hipGetLastError()) return bad("k_snap_rows", rc);
-    if (hipError_t rc = fields(true)) return bad("k_snap_field", rc);
-    return 0;
+    if (LaunchErr e = launch_err("k_snap_rows")) return e;
+    return launch_err("k_snap_field", fields(true));
   }
   if (qblocks) hipLaunchKernelGGL(k_snap_fill, dim3(a.n * qblocks), blk, 0, stream, a, qblocks);
-  if (hipError_t rc = hipGetLastError()) return bad("k_snap_fill", rc);
+  if (LaunchErr e = launch_err("k_snap_fill")) return e;
   if (rblocks) {
     hipLaunchKernelGGL(k_snap_live<false>, dim3(a.n * rblocks), blk, 0, stream, a, rblocks);
     hipLaunchKernelGGL(k_snap_scan_env, dim3(a.n), blk, 0, stream, a, false);
     hipLaunchKernelGGL(k_snap_rows<false>, dim3(a.n * rblocks), blk, 0, stream, a, rblocks);
   }
-  if (hipError_t rc = hipGetLastError()) return bad("k_snap_rows", rc);
-  if (hipError_t rc = fields(false)) return bad("k_snap_field", rc);
-  return 0;
+  if (LaunchErr e = launch_err("k_snap_rows")) return e;
+  return launch_err("k_snap_field", fields(false));
 }
 
 }  // namespace sfl

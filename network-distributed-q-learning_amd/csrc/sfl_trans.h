@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "sfl_core.h"
+#include "sfl_launch.h"
 
 namespace sfl {
 
@@ -352,8 +353,7 @@ inline void trans_host(const TransArgs& a) {
   *a.last_count = (int32_t)C;
 }
 
-// sfl_trans.hip: queues the two kernels on `stream` (a hipStream_t); 0, or -1 with the failing launch's name in *what and
-// HIP's error code in *code
-int trans_launch(const TransArgs& a, void* stream, const char** what, int* code);
+// sfl_trans.hip: queues the two kernels on `stream` (a hipStream_t); the failing launch, if any (sfl_launch.h)
+LaunchErr trans_launch(const TransArgs& a, void* stream);
 
 }  // namespace sfl

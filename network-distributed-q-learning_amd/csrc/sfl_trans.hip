@@ -194,22 +194,13 @@ __global__ void __launch_bounds__(BLOCK) k_trans_write(const TransArgs a, uint32
 
 namespace sfl {
 
-int trans_launch(const TransArgs& a, void* stream_, const char** what, int* code) {
+LaunchErr trans_launch(const TransArgs& a, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const uint32_t nb = (a.E + TRANS_BLOCK - 1) / TRANS_BLOCK;
   hipLaunchKernelGGL(k_trans_count, dim3(nb), dim3(TRANS_BLOCK), 0, stream, a);
-  if (hipError_t rc = hipGetLastError()) {
-    *what = "k_trans_count";
-    *code = (int)rc;
-    return -1;
-  }
+  if (LaunchErr e = launch_err("k_trans_count")) return e;
   hipLaunchKernelGGL(k_trans_write, dim3(nb), dim3(TRANS_BLOCK), 0, stream, a, nb);
-  if (hipError_t rc = hipGetLastError()) {
-    *what = "k_trans_write";
-    *code = (int)rc;
-    return -1;
-  }
-  return 0;
+  return launch_err("k_trans_write");
 }
 
 }  // namespace sfl

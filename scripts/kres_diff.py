@@ -8,7 +8,8 @@ that twin.  The "code" column says whether the
 kernel's machine code (the symbol's bytes in its code object's .text) is the same in both, or the same but for
 pc-relative addresses (same_code).  Exit status 1 if a kernel
 present in both differs in a resource field (registers, spills, scratch, LDS); code bytes alone do not fail.  The
-transition assembler's kernels (k_trans_count, k_trans_write: sfl_trans.hip) are listed by name.
+transition assembler's kernels (k_trans_count, k_trans_write: sfl_trans.hip) are listed by name, and so are the cell
+folds and their reset kernels (k_curve_*: sfl_curve.hip; k_eval_*: sfl_eval.hip).
 Usage: python scripts/kres_diff.py OLD.so NEW.so [--md]"""
 import re
 import struct
@@ -66,8 +67,9 @@ def kernels_of(co):
         # (Itanium mangling: k_waveILi8ELi2ELb1E...E -- integer and bool template arguments only)
         m = re.search(r"\d+(k_wave_g_bank|k_wave2_bank|k_wave_bank|k_wave_g|k_wave2_part|k_wave_part|k_wave2|k_wave)I((?:L[ib]\d+E)+)E", name)
         if not m:
-            # the transition assembler's kernels (sfl_trans.hip: no template arguments), listed by name
-            t = re.search(r"\d+(k_trans_[a-z]+)", name)
+            # the transition assembler's kernels (sfl_trans.hip) and the cell folds with their reset kernels
+            # (sfl_curve.hip, sfl_eval.hip): no template arguments, listed by name
+            t = re.search(r"\d+(k_(?:trans|curve|eval)_[a-z_]+)", name)
             if t:
                 vals = [int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in FIELDS]
                 out[t.group(1)] = vals + [size.get(name, -1), code.get(name)]

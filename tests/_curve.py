@@ -21,7 +21,8 @@ FIELDS = _lib.CURVE_FIELDS
 I64_MAX, I64_MIN = np.iinfo(np.int64).max, np.iinfo(np.int64).min
 
 # row: a tests/_shapes.ROWS map as (S, T); G: SFL_WAVE_G ("scalar": SFL_KERNEL=scalar, None: unset); E: envs (None:
-# 256 / G + 3); series: None (one series), ("mod", k) for env_series = e % k, "hpg" for a grouped handle with NULL series
+# 256 / G + 3); series: None (one series), ("mod", k) for env_series = e % k, ("lone", k) for env 0 alone on series
+# k - 1 and every other env on e % (k - 1), "hpg" for a grouped handle with NULL series
 # seed0: the envs run the seeds from seed0 upward (tests/_shapes.seeds starts at 300 too), STUCK left out
 Case = namedtuple("Case", "name row G max_steps chunks bin_episodes n_bins ring series E seed0",
                   defaults=(None, None, 300))
@@ -45,7 +46,11 @@ SHORT = Case("short", _row(5, 1), 16, 100_000, (15,) * 8, 8, 4, 16, seed0=309)
 LOST = Case("lost", _row(5, 1), 16, 100_000, (30, 55), 8, 4, 2)
 EDGES = tuple(Case(f"edges-{E}", _row(5, 1), None, 100_000, (15, 15), 4, 3, 16, ("mod", 5), E)
               for E in (1, 63, 64, 65, 257))
-CASES = (MIXED,) + FAMILIES + SERIES + (SHORT, LOST) + EDGES
+# env 0 alone on its series beside four series of 16 envs each in wavefront 0 (a lone lane and shared cells in one
+# wavefront: the fold notes the lone lane, goes on reducing the others and lets it issue its atomics after the loop);
+# env 64 is the only lane of wavefront 1
+LONE = Case("lone-65", _row(5, 1), None, 100_000, (15, 15), 4, 3, 16, ("lone", 5), 65)
+CASES = (MIXED,) + FAMILIES + SERIES + (SHORT, LOST) + EDGES + (LONE,)
 UNCHANGED = (Case("unchanged-16x16", _row(16, 16), 16, 40, (150, 250), 2, 3, 8, ("mod", 3)),
              Case("unchanged-5x1", _row(5, 1), 16, 100_000, (30, 55), 8, 4, 2))
 
@@ -88,7 +93,12 @@ def series_of(c):
         return None, 1
     if c.series == "hpg":
         return np.array(sh.env_groups(n)), len(sh.GROUPS)
-    return np.arange(n) % c.series[1], c.series[1]
+    kind, k = c.series
+    if kind == "lone":
+        ser = np.arange(n) % (k - 1)
+        ser[0] = k - 1
+        return ser, k
+    return np.arange(n) % k, k
 
 
 def make_batch(c, lib, curve=True, **kw):
@@ -241,6 +251,10 @@ def check_reference(c, rec, marks, kept, want):
         assert (want["lost"].sum(axis=1) > 0).sum() >= 2 and (kept == c.ring).all()
     if c.name.startswith("edges"):
         assert want["count"].sum() > 0 and (n < 5 or (want["count"].sum(axis=0) > 0).all())
+    if c.name.startswith("lone"):
+        ser = series_of(c)[0]
+        assert (ser == c.series[1] - 1).sum() == 1 and np.bincount(ser[:64])[:-1].min() >= 2  # alone beside shared series
+        assert want["count"][:, c.series[1] - 1].sum() > 0
 
 
 def step(b, c, d):

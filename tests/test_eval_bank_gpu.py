@@ -98,11 +98,14 @@ def test_copy_policy(lib, monkeypatch):
 
 def test_gpu_cells_equal_host_cells(lib, monkeypatch):
     """The device fold against the host build's fold of the same evaluation, with more envs than a wavefront per policy
-    and with every env on a policy of its own (the fold's two paths: the wave reduction and the lone lanes)."""
+    and with every env on a policy of its own (the fold's two paths: the wave reduction and the lone lanes), and with
+    env 7 alone on its policy in a wavefront whose other lanes share two (both paths in one wavefront: the lone lane is
+    noted while the loop goes on and issues its atomics after it)."""
     cell = BY_NAME["g8"]
     _select(monkeypatch, cell)
     n = 200
-    for P, pol in ((2, [0 if e % 5 else 1 for e in range(n)]), (n, list(range(n)))):
+    for P, pol in ((2, [0 if e % 5 else 1 for e in range(n)]), (n, list(range(n))),
+                   (3, [2 if e == 7 else 0 if e % 5 else 1 for e in range(n)])):
         tabs = eb.tables(cell.row)
         cells = []
         for L in (lib, hostsim.lib()):
