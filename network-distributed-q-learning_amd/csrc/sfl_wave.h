@@ -342,6 +342,14 @@ struct WEnv {
   // barrier.  Not in the 16-switch grouped shapes of handles with hyperparameter groups: there the new order alone
   // raised the scratch from 48 to 64 bytes per lane (scripts/kres_diff.py against the parent), so they keep the old one
   static constexpr bool PF_PIN = !(HPG && PPL == 8 && G < 64);
+  // the pending update's key-set row recomputed by post() from the slot word and the port record in LDS instead of
+  // carried from decide() in Dec::row_pend, which variant 7 spilled across the loop (G = 64: the port record is a
+  // scalar load there; PART: post_part() reads the owner's row table in decide())
+  static constexpr bool ROW_PEND_POST = !PART && G < 64;
+  // decide()'s epsilon load issued with its other reads that do not depend on the observation.  The fused learning
+  // shapes with vector table loads only: G = 64 reads the table through the scalar cache, the external-action, bank
+  // and partitioned shapes keep their order
+  static constexpr bool EPS_EARLY = !EXT && !BANK && !PART && G < 64 && !xp::kEpsConst && !xp::kNoRng;
   int pf_n = 0;  // RING: decisions since the batch was staged (= the record of the next one)
   static constexpr int kG = G;
   static_assert(TPL * G <= 128, "at most 128 train slots per env");
@@ -1866,6 +1874,14 @@ struct WEnv {
 #pragma unroll
     for (int i = 0; i < 5; ++i) rng_w[i] = lrng[i];
     const uint32_t n_sw = cget(sw);
+    // EPS_EARLY: the decision's epsilon, which needs the interaction count only, loaded here and held in front of
+    // the observation by a scheduling barrier: its round trip runs under the observe work instead of behind it
+    // (past the table nothing is loaded: the pow path below)
+    double eps_tab_v = 0.0;
+    if constexpr (EPS_EARLY) {
+      if (n_sw < (uint32_t)m.ntab) eps_tab_v = ld(eps_row(), (size_t)n_sw);
+      __builtin_amdgcn_sched_barrier(0);
+    }
     const Mask malf = malf_kept();
     const int pidx = PF_BY_RANK ? rec : h;  // the staged offsets' record
     const uint32_t pf_roff_h = rec_of(pf_roff, pidx), pf_qoff_h = rec_of(pf_qoff, pidx);
@@ -1943,7 +1959,7 @@ struct WEnv {
       const bool loc_p = local_sw(ps);
       if (!PART || loc_p) {
         d.qoff_pend = qoff_of(4 * ps + pslot, pr) + pstate * (uint32_t)pr.q_w() + (uint32_t)pj;
-        d.row_pend = rowb_of(4 * ps + pslot, pr) + pstate;
+        if constexpr (!ROW_PEND_POST) d.row_pend = rowb_of(4 * ps + pslot, pr) + pstate;
       }
       if (!loc_p) {
         // the pending update is applied by its row's owner (PART: d.qoff_pend stays PF_NONE; post_part emits the record)
@@ -1972,6 +1988,8 @@ struct WEnv {
       const double ud = Ud(pcg_double(rng));
       if (xp::kEpsConst) {
         explore = ud < eps0_();
+      } else if constexpr (EPS_EARLY) {
+        explore = ud < (n < (uint32_t)m.ntab ? eps_tab_v : eps0_() * pow_ool(eps_decay_(), (double)n));
       } else {
         explore = ud < (n < (uint32_t)m.ntab ? LDC(eps_row(), (size_t)n) : eps0_() * pow_ool(eps_decay_(), (double)n));
       }
@@ -2217,9 +2235,12 @@ struct WEnv {
     const bool hp = d.qoff_pend != PF_NONE;
     int ps = 0;
     double nv = 0.0;
+    uint32_t row_pend = d.row_pend;
     if (hp) {
       const uint32_t pend = slot_pend(d.slotword, epoch);
       ps = (int)(pend & 0xFFFu);
+      // ROW_PEND_POST: the pending update's key-set row from the port record in LDS, as decide() computed it
+      if constexpr (ROW_PEND_POST) row_pend = port_rec(4 * ps + (int)((pend >> 12) & 3u)).row_base() + ((pend >> 14) & 0x3FFFu);
       const double lr = lr_of(cget(ps));
       const double r = (double)d.reward;
       if (d.sw != ps) {
@@ -2240,7 +2261,7 @@ struct WEnv {
         if (rep == 1) asm volatile("" ::: "memory");
         if (hp) {
           if (!xp::kNoQStore && (rep == 0 || xp::kQStoreTwice)) st(qbase(), (size_t)d.qoff_pend, nv);
-          if (!xp::kNoTouch && (rep == 0 || xp::kTouchTwice)) touch_row(d.row_pend);
+          if (!xp::kNoTouch && (rep == 0 || xp::kTouchTwice)) touch_row(row_pend);
         }
         if (!xp::kNoTouch && (rep == 0 || xp::kTouchTwice) && (d.touch_cur || (hp && d.sw != ps))) touch_row(d.row_cur);
         if (!xp::kNoSlot && (rep == 0 || xp::kSlotTwice)) {
