@@ -8,7 +8,8 @@ when malfunctions are on, else 1, as in eval.py:85-97).
 scores each experiment's table on N seeded greedy episodes in one device batch (runtime.EvalBatch): experiments on the
 same scenario (equal [ENV] sections, and equal random_seed where the map is generated from it) share a batch as its
 policies, env i runs seed S + i (default S: the config's random_seed, so env 0 is the episode the plain evaluation
-runs), results go to EXP_DIR/eval_batch/summary.json and per_env.npz.
+runs), results go to EXP_DIR/eval_batch/summary.json and per_env.npz; with --diagnose [--stall S] every train that did
+not arrive is classified on the device as well (eval_batch/nonarrivals.json).
 """
 import argparse
 import configparser
@@ -64,7 +65,7 @@ def _scenario_key(config):
     return tuple(sorted(env.items())), None if from_file else int(config["MISC"]["random_seed"])
 
 
-def evaluate_batch(exp_dirs, n_envs, model_file="distr_q_model.pkl", seed0=None, lib=None):
+def evaluate_batch(exp_dirs, n_envs, model_file="distr_q_model.pkl", seed0=None, lib=None, diagnose=False, stall=30):
     """Each experiment's saved Q-table on ``n_envs`` greedy episodes, env i on seed ``seed0 + i`` (default ``seed0``:
     the experiment's ``random_seed``), in one device batch per group of experiments on the same scenario: the group's
     tables are the policies of one ``runtime.EvalBatch`` of ``len(group) * n_envs`` envs.  Experiments share a scenario
@@ -73,7 +74,10 @@ def evaluate_batch(exp_dirs, n_envs, model_file="distr_q_model.pkl", seed0=None,
     seed, so two seeds are two maps and two timetables.
     Writes ``EXP_DIR/eval_batch/summary.json`` (the policy's cell of the device-side reduction, its means, the seeds,
     the kernel variant and the kernel ms) and ``per_env.npz`` ([n_envs] arrays, ``delays`` and ``at_dest``
-    [n_envs][T], ``trains_at_dest`` as ``evaluate`` saves it for env 0).  Returns {exp_dir: summary}."""
+    [n_envs][T], ``trains_at_dest`` as ``evaluate`` saves it for env 0).  Returns {exp_dir: summary}.
+    With ``diagnose`` every train that did not arrive is classified on the device (``EvalBatch.diagnose`` with the window
+    ``stall``) and ``EXP_DIR/eval_batch/nonarrivals.json`` holds the policy's class counts, their per-episode means and
+    the ten cells with the most stalled trains as (row, column, count); the other files are what they are without it."""
     runtime = importlib.import_module(PKG + ".runtime")
     n_envs = int(n_envs)
     if n_envs < 1:
@@ -107,6 +111,9 @@ def evaluate_batch(exp_dirs, n_envs, model_file="distr_q_model.pkl", seed0=None,
                 ev.load_policy_dict(p, obj[0] if isinstance(obj, list) else obj)
             out = ev.evaluate([p for p in range(P) for _ in range(n_envs)])
             cnt = ev.counters()
+            if diagnose:
+                dg = ev.diagnose(stall, per_env=False)["table"]
+                hot = [ev.hotspots(p) for p in range(P)]
         finally:
             ev.close()
         for p, (exp_dir, _) in enumerate(members):
@@ -127,6 +134,14 @@ def evaluate_batch(exp_dirs, n_envs, model_file="distr_q_model.pkl", seed0=None,
             with open(os.path.join(out_dir, "summary.json"), "w") as f:
                 json.dump(summary, f, indent=1)
             results[exp_dir] = summary
+            if diagnose:
+                top = [int(i) for i in np.argsort(-hot[p].ravel().astype(np.int64), kind="stable")[:10] if hot[p].ravel()[i] > 0]
+                W = hot[p].shape[1]
+                rec = dict(exp_dir=exp_dir, policy=p, n_envs=n_envs, n_trains=int(env.compiled.T), stall=int(stall),
+                           cell={k: (float(v[p]) if v.dtype.kind == "f" else int(v[p])) for k, v in dg.items()},
+                           hot_cells=[[i // W, i % W, int(hot[p].ravel()[i])] for i in top])
+                with open(os.path.join(out_dir, "nonarrivals.json"), "w") as f:
+                    json.dump(rec, f, indent=1)
     return results
 
 
@@ -137,8 +152,11 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, default=0, metavar="N",
                     help="score each table on N seeded greedy episodes in one device batch (eval_batch/)")
     ap.add_argument("--seed0", type=int, default=None, help="with --batch: env i runs seed S + i (default: random_seed)")
+    ap.add_argument("--diagnose", action="store_true",
+                    help="with --batch: classify every non-arrival on the device (eval_batch/nonarrivals.json)")
+    ap.add_argument("--stall", type=int, default=30, help="with --diagnose: ticks without a move that make a train stalled")
     args = ap.parse_args()
     if args.batch > 0:
-        evaluate_batch(args.exp_dirs, args.batch, args.model, args.seed0)
+        evaluate_batch(args.exp_dirs, args.batch, args.model, args.seed0, diagnose=args.diagnose, stall=args.stall)
     else:
         evaluate(args.exp_dirs, args.model)

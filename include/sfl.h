@@ -608,6 +608,72 @@ int sfl_bank_eval(sfl_handle* h, const uint32_t* env_policy /* [n_envs] */, sfl_
 int sfl_bank_read(sfl_handle* h, sfl_eval_cell* out /* [n_policies] */);
 int sfl_bank_fold_ms(sfl_handle* h, double* last_ms, double* total_ms /* either may be NULL */);
 
+/* ---- policy-bank evaluation: every non-arrival classified on the device ----
+ * sfl_bank_eval says per train early, late or not arrived.  sfl_bank_diag says why a train did not arrive, with the
+ * classes of scripts/diagnose_nonarrivals.py (its `deadlock` split into queue and cycle), for every episode of the last
+ * sfl_bank_eval, from what that launch left on the device: each train's final cell, heading and state, and the tick
+ * of its last move, which the bank episode records.  THE RULE -- the host build, the kernels of sfl_diag.hip and the
+ * tests' restatement on the Python oracle implement it exactly; every word is an integer, nothing has a tolerance.
+ * For env e after its bank episode:
+ *   n            the episode's tick count (sfl_eval_out.ticks).
+ *   pos_i(h)     train h's cell after tick i; off the map is a value of its own, and pos_0 is off the map.
+ *   L(h)         the largest i in 1..n with pos_i(h) != pos_{i-1}(h), or 0 if there is none.
+ *   stalled_for(h) = n - L(h) for a train that is on the map at the end, and -1 otherwise.
+ *   stalled      on the map at the end and stalled_for(h) >= min(stall, n) - 1: the train's position after each of the
+ *                last `stall` ticks equals its final position (the script's window).
+ *   blocker(h)   for a stalled train: take MOVE_FORWARD, MOVE_LEFT, MOVE_RIGHT in that order; for each action that is
+ *                valid from the train's final (cell, heading) (move_tab: transition valid and new cell valid) take the
+ *                cell it leads to and the train with the highest handle that stands on it; if that train is stalled it
+ *                is blocker(h) and the search stops.  Otherwise, and for every train that is not stalled, -1.
+ *   on a cycle   stalled, and following blocker from h returns to h within T steps.
+ *   class, first match wins:
+ *     0 SFL_DIAG_ARRIVED         state DONE
+ *     1 SFL_DIAG_TRUNCATED       the episode was cut by max_steps (sfl_eval_out.truncated)
+ *     2 SFL_DIAG_NEVER_DEPARTED  off the map at the end
+ *     3 SFL_DIAG_MOVING_LATE     on the map, not stalled
+ *     4 SFL_DIAG_STOP_LOOP       stalled, blocker -1
+ *     5 SFL_DIAG_DEADLOCK_QUEUE  stalled, has a blocker, not on a cycle
+ *     6 SFL_DIAG_DEADLOCK_CYCLE  stalled, has a blocker, on a cycle
+ *   A train stalled in state MALFUNCTION is classified like any other stalled train and counted in a word of its own.
+ *   stalled_for, stalled and blocker do not depend on the class: a stalled train of a truncated episode has them too.
+ * sfl_diag_cell, per policy, over the episodes that followed it: the trains of classes 1 - 6 (the six class words and
+ *   the arrived trains sum to episodes * T); cycles: the trains of class 6 whose handle is the smallest of their cycle,
+ *   that is the distinct cycles; episodes_jammed: the episodes with a train of class 5 or 6; stalled_in_malfunction: the
+ *   stalled trains whose state is MALFUNCTION; stalled_for_sum / _max over the stalled trains (max: INT64_MIN if none).
+ * sfl_bank_diag classifies with the window `stall` (>= 1), on the handle's stream behind the evaluation; it may be
+ *   called again with another `stall` without a new evaluation, and changes no output of sfl_bank_eval and no env
+ *   state.  Every pointer of sfl_diag_out is an optional host array.  sfl_bank_diag_read: the cells of the last
+ *   sfl_bank_diag.  sfl_bank_diag_hot: per cell of the map, the trains of classes 4 - 6 of policy p's episodes that
+ *   stand on it.  sfl_bank_diag_ms: the device time of the last diagnosis and of all since create (0 on the host build;
+ *   never part of sfl_counters.last_kernel_ms).
+ * Refused, with a message in sfl_last_error and the handle usable: a handle that is no evaluation handle; no successful
+ *   sfl_bank_eval yet; stall < 1; p >= n_policies; sfl_bank_diag_read / sfl_bank_diag_hot before a successful
+ *   sfl_bank_diag of the last evaluation. */
+#define SFL_DIAG_ARRIVED         0
+#define SFL_DIAG_TRUNCATED       1
+#define SFL_DIAG_NEVER_DEPARTED  2
+#define SFL_DIAG_MOVING_LATE     3
+#define SFL_DIAG_STOP_LOOP       4
+#define SFL_DIAG_DEADLOCK_QUEUE  5
+#define SFL_DIAG_DEADLOCK_CYCLE  6
+typedef struct {            /* one policy's cell: 12 x int64 */
+  int64_t episodes;         /* envs that followed the table in the diagnosed sfl_bank_eval */
+  int64_t truncated, never_departed, moving_late, stop_loop, deadlock_queue, deadlock_cycle;  /* trains of classes 1 - 6 */
+  int64_t cycles;
+  int64_t episodes_jammed;
+  int64_t stalled_in_malfunction;
+  int64_t stalled_for_sum, stalled_for_max;
+} sfl_diag_cell;
+typedef struct {            /* optional host outputs of sfl_bank_diag */
+  uint8_t* cls;             /* [T][n_envs] SFL_DIAG_* */
+  int16_t* blocker;         /* [T][n_envs] train handle or -1 */
+  int32_t* stalled_for;     /* [T][n_envs] */
+} sfl_diag_out;
+int sfl_bank_diag(sfl_handle* h, int32_t stall, sfl_diag_out* out /* may be NULL */);
+int sfl_bank_diag_read(sfl_handle* h, sfl_diag_cell* out /* [n_policies] */);
+int sfl_bank_diag_hot(sfl_handle* h, uint32_t p, uint32_t* out /* [H*W] */);
+int sfl_bank_diag_ms(sfl_handle* h, double* last_ms, double* total_ms /* either may be NULL */);
+
 /* ---- suspend and resume: a batch's state and its live Q rows, packed on the device ----
  * Everything a launch leaves behind is the per-env state, the key set and the Q block of each env.  A capture of n
  * listed envs takes, per env in list order: one state record of state_bytes bytes; the key set ([touched_words]

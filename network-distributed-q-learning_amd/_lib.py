@@ -67,6 +67,10 @@ CURVE_XFIELDS = ("count", "lost", "arrived_sum", "arrived_min", "arrived_max", "
 EVAL_FIELDS = ("episodes", "trains_early", "trains_late", "trains_not_arrived", "arrived_min", "arrived_max", "all_arrived",
                "reward_sum", "reward_min", "reward_max", "decisions_sum", "ticks_sum", "malfunctions_sum",
                "delay_sum_arrived", "truncated")
+# include/sfl.h sfl_diag_cell: the 12 int64 words of a policy's non-arrival cell in order, and SFL_DIAG_* (class values)
+DIAG_FIELDS = ("episodes", "truncated", "never_departed", "moving_late", "stop_loop", "deadlock_queue", "deadlock_cycle",
+               "cycles", "episodes_jammed", "stalled_in_malfunction", "stalled_for_sum", "stalled_for_max")
+DIAG_CLASSES = ("arrived", "truncated", "never_departed", "moving_late", "stop_loop", "deadlock_queue", "deadlock_cycle")
 BANK_FROM_ENV = 0
 BANK_FROM_COHORT = 1
 CURVE_MAX_TABLE_BYTES = 64 << 20
@@ -102,6 +106,11 @@ class EvalOut(C.Structure):
     _fields_ = [("cum_reward", P(C.c_double)), ("arrived", P(C.c_int32)), ("malfunctions", P(C.c_int32)),
                 ("decisions", P(C.c_int32)), ("ticks", P(C.c_int32)), ("truncated", P(C.c_int32)),
                 ("delays", P(C.c_int32)), ("at_dest", P(C.c_uint8))]
+
+
+class DiagOut(C.Structure):
+    """sfl_diag_out: the optional per-train outputs of sfl_bank_diag."""
+    _fields_ = [("cls", P(C.c_uint8)), ("blocker", P(C.c_int16)), ("stalled_for", P(C.c_int32))]
 
 
 class StateDesc(C.Structure):
@@ -204,6 +213,10 @@ EXPORTS = {
     "sfl_bank_eval": (C.c_int, [C.c_void_p, P(C.c_uint32), P(EvalOut)]),
     "sfl_bank_read": (C.c_int, [C.c_void_p, P(C.c_int64)]),
     "sfl_bank_fold_ms": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double)]),
+    "sfl_bank_diag": (C.c_int, [C.c_void_p, C.c_int32, P(DiagOut)]),
+    "sfl_bank_diag_read": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "sfl_bank_diag_hot": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_uint32)]),
+    "sfl_bank_diag_ms": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double)]),
     # suspend and resume (runtime.Batch capture / restore / q_dicts)
     "sfl_state_info": (C.c_int, [C.c_void_p, P(StateDesc)]),
     "sfl_state_capture": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_uint32), P(C.c_uint64), P(C.c_uint64)]),

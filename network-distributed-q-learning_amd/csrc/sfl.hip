@@ -824,6 +824,14 @@ struct HipBackend {
     check(hipEventRecord(ev1, stream), "event");
     return err.empty() ? 0 : -1;
   }
+  // sfl_bank_diag: the kernels of sfl_diag.hip queued on the handle's stream between the two events (elapsed_ms()
+  // after the caller's sync is their time)
+  int diag(const sfl::DiagArgs& a) {
+    check(hipEventRecord(ev0, stream), "event");
+    if (sfl::LaunchErr le = sfl::diag_launch(a, (void*)stream)) return fail(le);
+    check(hipEventRecord(ev1, stream), "event");
+    return err.empty() ? 0 : -1;
+  }
   // sfl_state_*: one phase's kernels of sfl_snap.hip on the handle's stream, timed between the two events
   int snap(const sfl::SnapArgs& a, int phase, float* ms) {
     check(hipEventRecord(ev0, stream), "event");

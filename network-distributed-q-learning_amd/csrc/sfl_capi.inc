@@ -427,6 +427,30 @@ int sfl_bank_fold_ms(sfl_handle* h, double* last_ms, double* total_ms) {
   return 0;
 }
 
+// ---- the non-arrival diagnosis of the last evaluation (sfl_diag.h) ----
+int sfl_bank_diag(sfl_handle* h, int32_t stall, sfl_diag_out* out) {
+  if (!h) return sfl::fail("sfl_bank_diag: null handle");
+  return sfl::bank_diag(HH(h), stall, out);
+}
+
+int sfl_bank_diag_read(sfl_handle* h, sfl_diag_cell* out) {
+  if (!h) return sfl::fail("sfl_bank_diag_read: null handle");
+  return sfl::bank_diag_read(HH(h), out);
+}
+
+int sfl_bank_diag_hot(sfl_handle* h, uint32_t p, uint32_t* out) {
+  if (!h) return sfl::fail("sfl_bank_diag_hot: null handle");
+  return sfl::bank_diag_hot(HH(h), p, out);
+}
+
+int sfl_bank_diag_ms(sfl_handle* h, double* last_ms, double* total_ms) {
+  if (!h) return sfl::fail("sfl_bank_diag_ms: null handle");
+  if (!HH(h)->bank.on) return sfl::fail("sfl_bank_diag_ms: not an evaluation handle (sfl_create_eval)");
+  if (last_ms) *last_ms = HH(h)->bank.dg_last_ms;
+  if (total_ms) *total_ms = HH(h)->bank.dg_total_ms;
+  return 0;
+}
+
 // ---- suspend and resume (sfl_snap.h) ----
 int sfl_state_info(sfl_handle* h, sfl_state_desc* out) {
   if (!h) return sfl::fail("sfl_state_info: null handle");

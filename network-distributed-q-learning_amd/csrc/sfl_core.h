@@ -235,6 +235,9 @@ struct SflCtl {
   // delay, and per env whether the episode ended by truncation (its decisions exceed max_steps)
   uint8_t* ev_at_dest;       // [T][E]
   int32_t* ev_trunc;         // [E]
+  // MODE_BANK: per train the tick of its last move, L of include/sfl.h's sfl_bank_diag rule: the largest tick of the
+  // episode after which the train's cell (off the map counts as one) differs from the tick before, 0 if none
+  int32_t* ev_last_move;     // [T][E]
 };
 enum : int32_t { MODE_BANK = 3 };
 
@@ -704,8 +707,9 @@ SFL_FN void env_reset(V& v) {
 // (switch_env.py:296-401, 427-485; flatland_lite.RailEnv.step)
 // ---------------------------------------------------------------------------
 // sc_aux layout: pa 0-3 | ddir 4-5 | mover 6 | allowed 7 | given 8-11 | has_pred 12 | pred_valid 13
+// last_move: MODE_BANK's [T][E] record of each train's last move (SflCtl::ev_last_move), or null
 template <class V>
-SFL_FN void env_tick(V& v) {
+SFL_FN void env_tick(V& v, int32_t* last_move = nullptr) {
   const SflMap& m = v.m;
   const SflState& s = v.s;
   const int32_t t = ++v.now;
@@ -851,6 +855,7 @@ SFL_FN void env_tick(V& v) {
     if (npos != pos) {
       if (pos >= 0 && s.occ[v.ix(pos)] == (uint8_t)h) s.occ[v.ix(pos)] = 0xFF;
       if (npos >= 0) s.occ[v.ix(npos)] = (uint8_t)h;
+      if (last_move) last_move[v.ix(h)] = t;
     }
     if (mf > 0) mf -= 1;
     if (npos >= 0) saved = 0;
@@ -1319,6 +1324,7 @@ SFL_FN void env_run(const SflMap& m, const SflState& s, const SflCtl& c, uint32_
   d.state = 0;
   double cum = s.cum_reward[e];
   const bool test_mode = c.mode == 1 || c.mode == MODE_BANK;
+  int32_t* const last_move = c.ev_last_move;  // (MODE_BANK only: null otherwise)
   v.masks_load();
   while (true) {
     const bool busy = wave_any(phase == PH_DECIDE || phase == PH_POST);
@@ -1334,6 +1340,9 @@ SFL_FN void env_run(const SflMap& m, const SflState& s, const SflCtl& c, uint32_
         else v.flags &= ~F_GREEDY;
       }
       env_reset(v);
+      // (the bank episode's record of the trains' last moves is kept in its output buffer: the launch is that one episode)
+      if (last_move)
+        for (int h = 0; h < m.T; ++h) last_move[(size_t)h * s.E + e] = 0;
       cum = 0.0;
       phase = PH_TICK;
     } else if (phase == PH_TICK) {
@@ -1346,7 +1355,7 @@ SFL_FN void env_run(const SflMap& m, const SflState& s, const SflCtl& c, uint32_
 #pragma unroll
         for (int w = 0; w < V::kNW; ++w) live -= popc32(v.msk[1][w]);
         abytes += 36ull * (uint64_t)live;
-        env_tick(v);
+        env_tick(v, last_move);
         ticks++;
         if (v.flags & F_TERM) phase = (v.flags & F_INFLIGHT) ? PH_POST : PH_END;
         else if (!queue_empty(v)) phase = (v.flags & F_INFLIGHT) ? PH_POST : PH_DECIDE;

@@ -17,6 +17,7 @@
 #include "sfl_consensus.h"
 #include "sfl_core.h"
 #include "sfl_curve.h"
+#include "sfl_diag.h"
 #include "sfl_eval.h"
 #include "sfl_mfgen.h"
 #include "sfl_part.h"
@@ -161,6 +162,19 @@ struct Handle {
     bool folded = false;
     float last_ms = 0.f;
     double total_ms = 0.0;
+    // the non-arrival diagnosis (sfl_bank_diag*; sfl_diag.h): the tick of each train's last move, which
+    // the episode launch writes beside at_dest; what the classify pass makes of it; the cells; diagnosed: the last
+    // evaluation has been classified (sfl_bank_eval clears it)
+    int32_t* last_move = nullptr;   // [T][E]
+    uint8_t* dg_cls = nullptr;      // [T][E]
+    int16_t* dg_blocker = nullptr;  // [T][E]
+    int32_t* dg_sf = nullptr;       // [T][E]
+    int32_t* dg_aux = nullptr;      // [2][E]
+    uint32_t* dg_hot = nullptr;     // [P][H*W]
+    int64_t* dg_cells = nullptr;    // [P][DG_WORDS]
+    bool diagnosed = false;
+    float dg_last_ms = 0.f;
+    double dg_total_ms = 0.0;
   } bank;
   // suspend and resume (sfl_state_*; sfl_snap.h): the fingerprint of the map descriptor (create), each
   // row's first cell and width on the host and the device (built at the first call), the pending capture between
@@ -591,6 +605,13 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
     bk.delays = h->template dalloc<int32_t>(T * E);
     bk.at_dest = h->template dalloc<uint8_t>(T * E);
     bk.cells = h->template dalloc<int64_t>((size_t)n_policies * EV_WORDS);
+    bk.last_move = h->template dalloc<int32_t>(T * E);
+    bk.dg_cls = h->template dalloc<uint8_t>(T * E);
+    bk.dg_blocker = h->template dalloc<int16_t>(T * E);
+    bk.dg_sf = h->template dalloc<int32_t>(T * E);
+    bk.dg_aux = h->template dalloc<int32_t>(2 * E);
+    bk.dg_hot = h->template dalloc<uint32_t>((size_t)n_policies * HW);
+    bk.dg_cells = h->template dalloc<int64_t>((size_t)n_policies * DG_WORDS);
     m.bank_q = bk.q;
     m.bank_policy = bk.policy;
   }
@@ -1084,11 +1105,13 @@ int bank_eval(Handle<B>* h, const uint32_t* env_policy, sfl_eval_out* out) {
   c.st_delays = bk.delays;
   c.ev_at_dest = bk.at_dest;
   c.ev_trunc = bk.trunc;
+  c.ev_last_move = bk.last_move;
   c.launch_dec = h->d_launch_dec;
   c.launch_ticks = h->d_launch_ticks;
   c.launch_bytes = h->d_launch_bytes;
   float ms = 0.f;
   bk.folded = false;
+  bk.diagnosed = false;
   int rc = h->be.run(h->map, h->st, c, h->variant, &ms);
   h->last_kernel_ms = ms;
   EvalArgs a{};
@@ -1135,6 +1158,71 @@ int bank_read(Handle<B>* h, sfl_eval_cell* out) {
   if (!out) return fail("sfl_bank_read: null argument");
   if (!h->bank.folded) return fail("sfl_bank_read: no successful sfl_bank_eval yet");
   h->be.d2h(out, h->bank.cells, (size_t)h->bank.P * EV_WORDS * 8);
+  return h->be.sync() ? fail(h->be.error()) : 0;
+}
+
+// the non-arrival diagnosis of the last sfl_bank_eval (include/sfl.h sfl_bank_diag*; sfl_diag.h): the classify pass and
+// the fold queued on the handle's stream, the optional per-train outputs behind them
+template <class B>
+int bank_diag(Handle<B>* h, int32_t stall, sfl_diag_out* out) {
+  typename Handle<B>::Bank& bk = h->bank;
+  if (!bk.on) return fail("sfl_bank_diag: not an evaluation handle (sfl_create_eval)");
+  if (!bk.folded) return fail("sfl_bank_diag: no successful sfl_bank_eval yet");
+  if (stall < 1) return fail("sfl_bank_diag: stall " + std::to_string(stall) + " (the window is at least 1 tick)");
+  const size_t E = h->E, T = h->map.T;
+  DiagArgs a{};
+  a.E = h->E;
+  a.n_policies = bk.P;
+  a.HW = (uint32_t)h->map.HW;
+  a.T = h->map.T;
+  a.stall = stall;
+  a.wave = h->variant > 0 ? 1 : 0;
+  a.policy = bk.policy;
+  a.ticks = bk.ticks;
+  a.trunc = bk.trunc;
+  a.last_move = bk.last_move;
+  a.tr_pos = h->st.tr_pos;
+  a.tr_bits = h->st.tr_bits;
+  a.move_tab = h->map.move_tab;
+  a.cls = bk.dg_cls;
+  a.blocker = bk.dg_blocker;
+  a.stalled_for = bk.dg_sf;
+  a.env_aux = bk.dg_aux;
+  a.hot = bk.dg_hot;
+  a.cells = bk.dg_cells;
+  bk.diagnosed = false;
+  int rc = h->be.diag(a);  // (timed on its own: elapsed_ms after the sync below)
+  if (!rc && out) {
+    if (out->cls) h->be.d2h_async(out->cls, bk.dg_cls, T * E);
+    if (out->blocker) h->be.d2h_async(out->blocker, bk.dg_blocker, T * E * 2);
+    if (out->stalled_for) h->be.d2h_async(out->stalled_for, bk.dg_sf, T * E * 4);
+  }
+  if (!rc) rc = h->be.sync();
+  if (rc) return fail(std::string("sfl_bank_diag: ") + h->be.error());
+  bk.dg_last_ms = h->be.elapsed_ms();
+  bk.dg_total_ms += bk.dg_last_ms;
+  bk.diagnosed = true;
+  return 0;
+}
+
+template <class B>
+int bank_diag_read(Handle<B>* h, sfl_diag_cell* out) {
+  if (!h->bank.on) return fail("sfl_bank_diag_read: not an evaluation handle (sfl_create_eval)");
+  if (!out) return fail("sfl_bank_diag_read: null argument");
+  if (!h->bank.folded) return fail("sfl_bank_diag_read: no successful sfl_bank_eval yet");
+  if (!h->bank.diagnosed) return fail("sfl_bank_diag_read: no successful sfl_bank_diag of the last evaluation yet");
+  h->be.d2h(out, h->bank.dg_cells, (size_t)h->bank.P * DG_WORDS * 8);
+  return h->be.sync() ? fail(h->be.error()) : 0;
+}
+
+template <class B>
+int bank_diag_hot(Handle<B>* h, uint32_t p, uint32_t* out) {
+  if (int rc = bank_check(h, "sfl_bank_diag_hot", p)) return rc;
+  if (!out) return fail("sfl_bank_diag_hot: null argument");
+  if (!h->bank.folded) return fail("sfl_bank_diag_hot: no successful sfl_bank_eval yet");
+  if (!h->bank.diagnosed) return fail("sfl_bank_diag_hot: no successful sfl_bank_diag of the last evaluation yet");
+  const size_t HW = (size_t)h->map.HW;
+  h->be.d2h(out, h->bank.dg_hot + (size_t)p * HW, HW * 4);
   return h->be.sync() ? fail(h->be.error()) : 0;
 }
 

@@ -101,6 +101,12 @@ struct HostBackend {
     sfl::eval_fold_host(a);
     return 0;
   }
+  // sfl_bank_diag: the classify pass and the fold as plain loops (sfl_diag.h)
+  int diag(const sfl::DiagArgs& a) {
+    sfl::diag_classify_host(a);
+    sfl::diag_fold_host(a);
+    return 0;
+  }
   // sfl_state_*: one phase as plain loops (sfl_snap.h)
   int snap(const sfl::SnapArgs& a, int phase, float* ms) {
     sfl::snap_host(a, phase);

@@ -281,6 +281,15 @@ struct PortRec {
   __device__ __forceinline__ uint32_t row_base() const { return w[2]; }
   __device__ __forceinline__ uint32_t q_off() const { return w[3]; }
 };
+// BANK: per train slot of the lane, the tick of the train's last move (SflCtl::ev_last_move), kept by tick().  An empty
+// base everywhere else, so that WEnv's members -- and with them the code of every other instantiation -- are what they
+// were (a member among the others changed the register assignment of kernels that never touch it)
+template <bool ON, int N>
+struct LastMove {
+  int32_t last_mv[N];
+};
+template <int N>
+struct LastMove<false, N> {};
 // G lanes per env (a lane group; G = 64: one env per wavefront, G = 32 / 16: two / four envs per
 // wavefront, for maps with few trains).  PPL semaphore words (ports <= G*PPL) and SPL counter words
 // (switches <= G*SPL) per lane.  With G = 64 the env's control values are wave-uniform and live in
@@ -309,7 +318,7 @@ struct PortRec {
 // where the table's base pointer is held instead): see qbase()
 template <int PPL, int SPL, int TWc, bool PART = false, int G = 64, bool LM = false, bool HPG = false, bool EXT = false,
           bool BANK = false>
-struct WEnv {
+struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
   static_assert(!(BANK && (PART || HPG || EXT)), "policy-bank evaluation: the plain shapes (and the LM one) only");
   static_assert(!(HPG && PART), "hyperparameter groups are not part of the partitioned local step");
   static_assert(!(EXT && (PART || HPG || LM)), "external-action mode: the plain shapes only");
@@ -442,6 +451,10 @@ struct WEnv {
     for (int k = 0; k < TPL; ++k) mine[k] = lane + G * k < m_.T;
 #pragma unroll
     for (int k = 0; k < PFS; ++k) pf_roff[k] = pf_qoff[k] = PF_NONE;
+    if constexpr (BANK) {
+#pragma unroll
+      for (int k = 0; k < TPL; ++k) this->last_mv[k] = 0;
+    }
     lpi = (uint32_t*)(lpf + PF_SLOTS * PF_D);
     lrng = (uint64_t*)(lds + G * (PPL + SPL) + PF_SLOTS * PF_WORDS);
     // PART: the timetable rows are read from the map (L2-resident): a launch runs one or two
@@ -1197,6 +1210,7 @@ struct WEnv {
         plan[k] = 0;
         nprv[k] = (nprv[k] & 0xFFFF0000u) | (t_init >> 16);
         delay[k] = ltt[8 * hk + 6];
+        if constexpr (BANK) this->last_mv[k] = 0;
       }
     }
 #pragma unroll
@@ -1454,6 +1468,7 @@ struct WEnv {
         done[k] = (st_ == S_DONE) || over;
         newdone[k] = done[k] && !tb_done(b);
         isdone[k] = st_ == S_DONE;
+        if constexpr (BANK) this->last_mv[k] = np != p0 ? t : this->last_mv[k];
         pos[k] = np;
         // switchfl: deviation fix
         if ((aux[k] >> 12) & 1u) {
@@ -2479,6 +2494,7 @@ struct WEnv {
       if (mine[k]) {
         st(c.st_delays, (size_t)hk * E + e, delay[k]);
         st(c.ev_at_dest, (size_t)hk * E + e, (uint8_t)(tb_state(bits[k]) == S_DONE ? 1 : 0));
+        st(c.ev_last_move, (size_t)hk * E + e, this->last_mv[k]);
       }
     }
   }

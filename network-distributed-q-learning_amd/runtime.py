@@ -898,6 +898,67 @@ class EvalBatch:
         return float(last.value), float(total.value)
 
 
+    # ---- why trains did not arrive ----
+    def diagnose(self, stall: int = 30, per_env: bool = True) -> Dict[str, object]:
+        """Classify every train of every episode of the last ``evaluate`` on the device (include/sfl.h sfl_bank_diag
+        states the rule; ``CLASS_NAMES`` names the values): a train is stalled when it stood on its final cell over the
+        last ``stall`` ticks.  May be called again with another ``stall`` without evaluating again.  Returns, with
+        ``per_env``, ``cls`` (uint8), ``blocker`` (int16, -1: none) and ``stalled_for`` (int32, -1: off the map) as
+        [T][E]; and ``table``: the int64 fields of sfl_diag_cell (``_lib.DIAG_FIELDS``) as [P] arrays, reduced on the
+        device, plus per-episode means ``<class>_mean`` of the six class counts and ``jammed_frac`` -- NaN where a
+        policy has no episode."""
+        E, T = self.E, self.cm.T
+        out: Dict[str, object] = {}
+        o = _lib.DiagOut()
+        if per_env:
+            out = dict(cls=np.zeros((T, E), np.uint8), blocker=np.zeros((T, E), np.int16),
+                       stalled_for=np.zeros((T, E), np.int32))
+            o.cls = _ptr(out["cls"], C.c_uint8)
+            o.blocker = _ptr(out["blocker"], C.c_int16)
+            o.stalled_for = _ptr(out["stalled_for"], C.c_int32)
+        stall = int(stall)
+        if not -2**31 <= stall < 2**31:
+            raise ValueError("diagnose: stall out of range")
+        self.lib.check(self.lib.dll.sfl_bank_diag(self.h, stall, C.byref(o)), "sfl_bank_diag")
+        cells = np.zeros((self.P, len(_lib.DIAG_FIELDS)), np.int64)
+        self.lib.check(self.lib.dll.sfl_bank_diag_read(self.h, _ptr(cells, C.c_int64)), "sfl_bank_diag_read")
+        out["stall"] = stall
+        out["table"] = diag_table(cells)
+        return out
+
+    def hotspots(self, p: int) -> np.ndarray:
+        """[H][W] uint32: per cell of the map, the stalled trains (classes stop_loop, deadlock_queue, deadlock_cycle) of
+        policy ``p``'s episodes that stand on it, from the last ``diagnose``."""
+        if int(p) < 0 or int(p) > 0xFFFFFFFF:
+            raise ValueError("hotspots: policy id out of range")
+        hot = np.zeros((self.cm.H, self.cm.W), np.uint32)
+        self.lib.check(self.lib.dll.sfl_bank_diag_hot(self.h, int(p), _ptr(hot, C.c_uint32)), "sfl_bank_diag_hot")
+        return hot
+
+    def diag_ms(self) -> Tuple[float, float]:
+        """Device ms of the last diagnosis (classify and fold) and of all of this handle (never part of
+        ``counters()['last_kernel_ms']``)."""
+        last, total = C.c_double(0.0), C.c_double(0.0)
+        self.lib.check(self.lib.dll.sfl_bank_diag_ms(self.h, C.byref(last), C.byref(total)), "sfl_bank_diag_ms")
+        return float(last.value), float(total.value)
+
+
+# include/sfl.h SFL_DIAG_*: the class a diagnosis gives a train, by value
+CLASS_NAMES = dict(enumerate(_lib.DIAG_CLASSES))
+
+
+def diag_table(cells: np.ndarray) -> Dict[str, np.ndarray]:
+    """sfl_diag_cell words [P][12] as one [P] int64 array per field plus, per episode, the means of the six class counts
+    (``truncated_mean`` ... ``deadlock_cycle_mean``) and ``jammed_frac`` (NaN without episodes)."""
+    t = {k: np.ascontiguousarray(cells[:, i]) for i, k in enumerate(_lib.DIAG_FIELDS)}
+    n = t["episodes"].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for k in _lib.DIAG_CLASSES[1:]:
+            t[k + "_mean"] = np.where(n > 0, t[k] / n, np.nan)
+        t["jammed_frac"] = np.where(n > 0, t["episodes_jammed"] / n, np.nan)
+    return t
+
+
 def eval_table(cells: np.ndarray) -> Dict[str, np.ndarray]:
     """sfl_eval_cell words [P][15] as one [P] int64 array per field plus the per-episode means (NaN without episodes)."""
     t = {k: np.ascontiguousarray(cells[:, i]) for i, k in enumerate(_lib.EVAL_FIELDS)}

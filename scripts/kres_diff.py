@@ -9,7 +9,8 @@ kernel's machine code (the symbol's bytes in its code object's .text) is the sam
 pc-relative addresses (same_code).  Exit status 1 if a kernel
 present in both differs in a resource field (registers, spills, scratch, LDS); code bytes alone do not fail.  The
 transition assembler's kernels (k_trans_count, k_trans_write: sfl_trans.hip) are listed by name, and so are the cell
-folds and their reset kernels (k_curve_*: sfl_curve.hip; k_eval_*: sfl_eval.hip).
+folds and their reset kernels (k_curve_*: sfl_curve.hip; k_eval_*: sfl_eval.hip) and the non-arrival diagnosis's
+kernels (k_diag_*: sfl_diag.hip).
 Usage: python scripts/kres_diff.py OLD.so NEW.so [--md]"""
 import re
 import struct
@@ -69,7 +70,7 @@ def kernels_of(co):
         if not m:
             # the transition assembler's kernels (sfl_trans.hip) and the cell folds with their reset kernels
             # (sfl_curve.hip, sfl_eval.hip): no template arguments, listed by name
-            t = re.search(r"\d+(k_(?:trans|curve|eval)_[a-z_]+)", name)
+            t = re.search(r"\d+(k_(?:trans|curve|eval|diag)_[a-z_]+)", name)
             if t:
                 vals = [int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in FIELDS]
                 out[t.group(1)] = vals + [size.get(name, -1), code.get(name)]
