@@ -400,7 +400,7 @@ __device__ __forceinline__ void part_answer_fast(const sfl::SflMap& m, const sfl
     if (a == na - 1) return col(w - 1);
     const uint32_t src = ((a < 4 ? srcw.x : srcw.y) >> (8 * (a & 3))) & 0xFFu;
     if (src == (uint32_t)slot) return col((int)(((a < 4 ? jw.x : jw.y) >> (8 * (a & 3))) & 0xFFu));
-    return m.default_q;
+    return m.dec.default_q;
   };
   double mx = val(0);
   int best = 0;
@@ -561,13 +561,13 @@ __global__ void k_qinit(sfl::SflMap m, sfl::SflState s, uint32_t n_rows, const u
   const uint32_t e = (uint32_t)(i / n_rows), r = (uint32_t)(i % n_rows);
   const uint32_t g = port[r], st = state[r];
   const int w = m.q_w[g];
-  double* row = s.q + (size_t)e * m.q_per_env + m.q_off[g] + (size_t)st * w;
+  double* row = s.lrn.q + (size_t)e * m.lrn.q_per_env + m.q_off[g] + (size_t)st * w;
   for (int j = 0; j < w; ++j) {
     const double v = vals[(size_t)r * 4 + j];
-    row[j] = (v != v) ? m.default_q : v;
+    row[j] = (v != v) ? m.dec.default_q : v;
   }
   const uint32_t rid = m.row_base[g] + st;
-  atomicOr(&s.touched[(size_t)e * m.touched_words + (rid >> 5)], 1u << (rid & 31u));
+  atomicOr(&s.lrn.touched[(size_t)e * m.lrn.touched_words + (rid >> 5)], 1u << (rid & 31u));
 }
 
 // A kernel's parameter structs in device memory: SflMap | SflState | SflCtl [| Tail], each at a 64-byte boundary

@@ -131,8 +131,8 @@ int sfl_get_q(sfl_handle* h, uint32_t env, double* q, uint32_t* touched) {
   if (int rc = no_eval(hh, "sfl_get_q", "has no per-env table; use sfl_bank_get")) return rc;
   if (env >= hh->E) return sfl::fail("sfl_get_q: env out of range");
   if (hh->part.world) return sfl::fail("sfl_get_q: the handle is graph-partitioned (use sfl_part_get_q)");
-  if (q) hh->be.d2h(q, hh->st.q + (size_t)env * hh->map.q_per_env, hh->map.q_per_env * 8);
-  if (touched) hh->be.d2h(touched, hh->st.touched + (size_t)env * hh->map.touched_words, hh->map.touched_words * 4);
+  if (q) hh->be.d2h(q, hh->st.lrn.q + (size_t)env * hh->map.lrn.q_per_env, hh->map.lrn.q_per_env * 8);
+  if (touched) hh->be.d2h(touched, hh->st.lrn.touched + (size_t)env * hh->map.lrn.touched_words, hh->map.lrn.touched_words * 4);
   return hh->be.sync() ? sfl::fail(hh->be.error()) : 0;
 }
 
@@ -141,8 +141,8 @@ int sfl_set_q(sfl_handle* h, uint32_t env, const double* q, const uint32_t* touc
   if (int rc = no_eval(hh, "sfl_set_q", "has no per-env table; use sfl_bank_set")) return rc;
   if (env >= hh->E) return sfl::fail("sfl_set_q: env out of range");
   if (hh->part.world) return sfl::fail("sfl_set_q: the handle is graph-partitioned");
-  if (q) hh->be.h2d(hh->st.q + (size_t)env * hh->map.q_per_env, q, hh->map.q_per_env * 8);
-  if (touched) hh->be.h2d(hh->st.touched + (size_t)env * hh->map.touched_words, touched, hh->map.touched_words * 4);
+  if (q) hh->be.h2d(hh->st.lrn.q + (size_t)env * hh->map.lrn.q_per_env, q, hh->map.lrn.q_per_env * 8);
+  if (touched) hh->be.h2d(hh->st.lrn.touched + (size_t)env * hh->map.lrn.touched_words, touched, hh->map.lrn.touched_words * 4);
   return hh->be.sync() ? sfl::fail(hh->be.error()) : 0;
 }
 

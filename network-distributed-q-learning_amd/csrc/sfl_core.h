@@ -18,6 +18,7 @@
 // contiguous block per env) because rows are gathered at data-dependent
 // offsets.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include <type_traits>
@@ -53,18 +54,45 @@ constexpr int MAXW = 4;  // train bitmask words (T <= 128)
 constexpr uint32_t PEND_NONE = 0xFFFFFFFFu;
 constexpr uint16_t PORT_NONE = 0xFFFFu;
 
-struct SflMap {
-  int32_t H, W, S, T, K, NP, HW, cell_bits;  // cell_bits: bits of a cell index (HW - 1)
-  int32_t max_episode_steps, mf_min, mf_max, ntab;
+// The learner's scalars of a decision, in three 32-byte blocks at the head of SflMap: what decide() reads (dec and
+// lrn, bytes 0-63) and what post() reads (lrn and upd, bytes 32-95) are each one aligned run, so a wave kernel
+// copies its phase's blocks in one place (a wide scalar load per block, one wait) instead of loading each field
+// where it is used.  Every field exists here only: whoever changes one (the tables and ntab, seedseq32) changes
+// the copy every reader sees.
+struct alignas(32) MapDecide {
   int32_t delay_thr;  // StandardObserver.delay_threshold (observer.py:221)
-  double mf_rate, gamma, eps0, eps_decay, lr0, lr_decay, default_q;
+  int32_t K;
+  const double* eps_tab;
+  const uint32_t* seedseq32;  // [2^31] first 32-bit output of Generator(PCG64(SeedSequence(v))), or null
+  double default_q;
+};
+struct alignas(32) MapLearn {
+  int32_t ntab, S;
+  int32_t ST;  // S * T, the (switch, train) slot words of an env (set with S and T when the map is built)
+  uint32_t touched_words;
+  uint64_t q_per_env;
+  const double* lr_tab;
+};
+struct alignas(32) MapUpdate {
+  double gamma, lr0, lr_decay;
+};
+static_assert(sizeof(MapDecide) == 32 && alignof(MapDecide) == 32, "decide()'s block: one 32-byte scalar load");
+static_assert(sizeof(MapLearn) == 32 && alignof(MapLearn) == 32, "the shared block: one 32-byte scalar load");
+static_assert(sizeof(MapUpdate) == 32 && alignof(MapUpdate) == 32, "post()'s block: one 32-byte scalar load");
+
+struct SflMap {
+  MapDecide dec;
+  MapLearn lrn;
+  MapUpdate upd;
+  int32_t H, W, T, NP, HW, cell_bits;  // cell_bits: bits of a cell index (HW - 1)
+  int32_t max_episode_steps, mf_min, mf_max;
+  double mf_rate, eps0, eps_decay;
   // the counter-based malfunction draw without its f64 conversion and 64-bit division (mf_propose):
   // u < mf_rate  <=>  (z >> 11) < mf_thresh = ceil(mf_rate * 2^53), and x % mf_n via mf_magic = (2^64 - 1) / mf_n
   uint64_t mf_thresh, mf_magic;
   uint32_t mf_n;
   int64_t max_steps;
-  uint64_t q_per_env;
-  uint32_t rows_per_env, touched_words;
+  uint32_t rows_per_env;
   const uint16_t* grid;
   const int16_t* cell_sw;
   const uint8_t* sw_np;
@@ -93,8 +121,6 @@ struct SflMap {
   const int32_t* tr_init_delay;
   const uint8_t* tr_init_dir;
   const int16_t* tr_init_port;
-  const double* eps_tab;
-  const double* lr_tab;
   // packed copies for the one-env-per-wave kernel (sfl_wave.h), built at create time
   const uint32_t* sw_pack;    // [S][16]: np | na<<4; src/dst 2b per action; turn/j 2b; q_w 4b per slot; row map per slot;
                               // neighbour port of ports 0-3 (16 b each) in words 8-9; 10-15 spare
@@ -103,7 +129,6 @@ struct SflMap {
   const uint32_t* move2c_tab; // [H*W][4 dir][4 action&3][4 rail action t]: move_tab's word of rail action t at the
                               // destination of (cell, dir, action); off the grid: that destination (cell -1)
   const int32_t* tr_pack;     // [T][8]: ed, la, k, target, init_cell, init_dist, init_delay, init_dir | init_port<<16
-  const uint32_t* seedseq32;  // [2^31] first 32-bit output of Generator(PCG64(SeedSequence(v))), or null
   const uint32_t* port_tr;    // [NP][4]: transition recipe of an out port o: nb(o) | unique(nb(o)) << 16;
                               //          nb(unique) | len(o) << 16; len(unique); 0  (int16 fields, -1 = none)
   // Flatland-compatible malfunction stream (sfl_mfgen.h): [E][mf_steps][T] num_broken_steps proposed at
@@ -124,6 +149,8 @@ struct SflMap {
   const double* bank_q;
   const uint32_t* bank_policy;  // [E], the table each env follows in the current sfl_bank_eval
 };
+static_assert(offsetof(SflMap, dec) == 0 && offsetof(SflMap, lrn) == 32 && offsetof(SflMap, upd) == 64,
+              "decide() reads bytes 0-63 of the map, post() bytes 32-95");
 enum : int { HPG_EPS0 = 0, HPG_EPS_DECAY = 1, HPG_LR0 = 2, HPG_LR_DECAY = 3 };
 
 // x % n for 1 <= n < 2^32 with M = floor((2^64 - 1) / n): q = hi64(x * M) is floor(x / n) or one less (M is
@@ -166,6 +193,14 @@ SFL_FN uint32_t mf_propose(const SflMap& m, uint64_t seed, uint32_t e, int32_t t
   return (uint32_t)(m.mf_min + (int32_t)r) + 1u;
 }
 
+// the learner's arrays of SflState, one 32-byte block like the map's (a phase's addresses from one scalar load)
+struct alignas(32) StateLearn {
+  uint64_t* slot;       // pending update | reward | epoch: [S*T][E] (k_run), [E][T][S] (k_wave)
+  uint32_t* counts;     // [S][E] agent_num_interactions
+  double* q;            // [E][q_per_env]
+  uint32_t* touched;    // [E][touched_words] Q-table key set
+};
+static_assert(sizeof(StateLearn) == 32 && alignof(StateLearn) == 32, "the learner's pointers: one 32-byte scalar load");
 struct SflState {
   uint32_t E;
   int32_t* phase;
@@ -200,11 +235,9 @@ struct SflState {
   uint8_t* occ;         // [H*W][E] occupying train or 0xFF
   uint8_t* claim;       // [H*W][E] motion-check claim or 0xFF
   uint64_t* sem;        // [NP][E] semaphore records
-  uint64_t* slot;       // pending update | reward | epoch: [S*T][E] (k_run), [E][T][S] (k_wave)
-  uint32_t* counts;     // [S][E] agent_num_interactions
-  double* q;            // [E][q_per_env]
-  uint32_t* touched;    // [E][touched_words] Q-table key set
+  StateLearn lrn;
 };
+static_assert(offsetof(SflState, lrn) % 32 == 0, "the learner's pointers: one aligned 32-byte run");
 
 struct SflCtl {
   int32_t mode;          // 0 = learn, 1 = greedy test, MODE_BANK = a greedy test on the policy bank (SflMap::bank_q)
@@ -527,7 +560,7 @@ struct Env {
       sem_set(p, sem_pack(h, is_in, now, now + span));
   }
   SFL_FN void free_switch_ports(int sw, int h) {
-    if (sw < 0 || sw >= m.S) {
+    if (sw < 0 || sw >= m.lrn.S) {
       err |= E_PORT;
       return;
     }
@@ -589,41 +622,41 @@ struct Env {
   SFL_FN double* qrow(int sw, int slot, uint32_t state) const {
     const int g = 4 * sw + slot;
     // (an evaluation handle: the env's table of the bank, which is never written -- env_run posts nothing when greedy)
-    double* base = m.bank_q ? const_cast<double*>(m.bank_q) + (size_t)m.bank_policy[e] * m.q_per_env
-                            : s.q + (size_t)e * m.q_per_env;
+    double* base = m.bank_q ? const_cast<double*>(m.bank_q) + (size_t)m.bank_policy[e] * m.lrn.q_per_env
+                            : s.lrn.q + (size_t)e * m.lrn.q_per_env;
     return base + m.q_off[g] + (size_t)state * m.q_w[g];
   }
   SFL_FN void touch(int sw, int slot, uint32_t state) const {
     if (m.bank_q) return;  // the bank is read-only: a greedy run's key-set inserts (max_action's __check_entry) are not recorded
     const uint32_t row = m.row_base[4 * sw + slot] + state;
-    s.touched[(size_t)e * m.touched_words + (row >> 5)] |= 1u << (row & 31u);
+    s.lrn.touched[(size_t)e * m.lrn.touched_words + (row >> 5)] |= 1u << (row & 31u);
   }
   // hyperparameter groups (SflMap::env_group): the env's group's table rows and scalars, else the map's own
   SFL_FN double eps_of(uint32_t n) const {
     if (m.env_group) {
       const size_t g = m.env_group[e];
-      if (n < (uint32_t)m.ntab) return m.hpg_eps_tab[g * (uint32_t)m.ntab + n];
+      if (n < (uint32_t)m.lrn.ntab) return m.hpg_eps_tab[g * (uint32_t)m.lrn.ntab + n];
       return m.hpg_sc[g * 4 + HPG_EPS0] * pow(m.hpg_sc[g * 4 + HPG_EPS_DECAY], (double)n);
     }
-    return n < (uint32_t)m.ntab ? m.eps_tab[n] : m.eps0 * pow(m.eps_decay, (double)n);
+    return n < (uint32_t)m.lrn.ntab ? m.dec.eps_tab[n] : m.eps0 * pow(m.eps_decay, (double)n);
   }
   // beyond the table: eps only decides `random() < eps` (an ulp of pow moves that by ~1e-17 in
   // probability), but lr enters the Q values, so on the device a decaying lr past the table is an error
   SFL_FN double lr_of(uint32_t n, uint32_t& err) const {
     if (m.env_group) {
       const size_t g = m.env_group[e];
-      if (n < (uint32_t)m.ntab) return m.hpg_lr_tab[g * (uint32_t)m.ntab + n];
+      if (n < (uint32_t)m.lrn.ntab) return m.hpg_lr_tab[g * (uint32_t)m.lrn.ntab + n];
       const double lr_decay = m.hpg_sc[g * 4 + HPG_LR_DECAY];
 #if defined(__HIP_DEVICE_COMPILE__)
       if (lr_decay != 1.0) err |= E_LR_TABLE;
 #endif
       return m.hpg_sc[g * 4 + HPG_LR0] * pow(lr_decay, (double)n);
     }
-    if (n < (uint32_t)m.ntab) return m.lr_tab[n];
+    if (n < (uint32_t)m.lrn.ntab) return m.lrn.lr_tab[n];
 #if defined(__HIP_DEVICE_COMPILE__)
-    if (m.lr_decay != 1.0) err |= E_LR_TABLE;
+    if (m.upd.lr_decay != 1.0) err |= E_LR_TABLE;
 #endif
-    return m.lr0 * pow(m.lr_decay, (double)n);
+    return m.upd.lr0 * pow(m.upd.lr_decay, (double)n);
   }
 
   // rng ------------------------------------------------------------------------
@@ -692,7 +725,7 @@ SFL_FN void env_reset(V& v) {
   // new (switch, train) epoch: slots from older episodes read as empty
   v.epoch = (v.epoch + 1u) & 0xFFu;
   if (v.epoch == 0) {
-    for (int i = 0; i < m.S * m.T; ++i) s.slot[v.ix(i)] = slot_make(PEND_NONE, 0, 0);
+    for (int i = 0; i < m.lrn.S * m.T; ++i) s.lrn.slot[v.ix(i)] = slot_make(PEND_NONE, 0, 0);
     v.epoch = 1;
   }
   s.cum_reward[v.e] = 0.0;
@@ -910,7 +943,7 @@ SFL_FN void env_tick(V& v, int32_t* last_move = nullptr) {
     else if ((st == S_STOPPED || st == S_MALF) && tb_prev(b) == A_STOP) sw = sw_at;
     else if (st == S_STOPPED || st == S_MALF) sw = v.next_port(h) >> 2;
     else continue;
-    if (sw >= m.S) {  // next port is None: the reference would raise here
+    if (sw >= m.lrn.S) {  // next port is None: the reference would raise here
       v.err |= E_PORT;
       continue;
     }
@@ -949,7 +982,7 @@ SFL_FN double row_val(const V& v, int sw, int slot, const double* row, int a) {
   const int na = m.sw_na[sw];
   if (a == na - 1) return row[m.q_w[4 * sw + slot] - 1];
   if (m.act_src[sw * 8 + a] == (uint8_t)slot) return row[m.act_j[sw * 8 + a]];
-  return m.default_q;
+  return m.dec.default_q;
 }
 
 // np.argmax over the full row, falling back to the first allowed maximum (distr_q.py:468-490)
@@ -1060,8 +1093,8 @@ SFL_FN void decide_observe(V& v, Obs& o, bool greedy) {
   const int32_t pos = v.pos(h);
   const int32_t delay = v.now - m.tr_la[h] + v.dist(h, pos, (int)tb_dir(b));
   const int32_t avail = m.tr_la[h] - m.tr_ed[h];
-  const uint32_t lvl = delay <= 0 ? 0u : (delay <= (int64_t)avail * m.delay_thr ? 1u : 2u);
-  const uint32_t state = ((free_bits * (uint32_t)m.K) + (uint32_t)m.tr_k[h]) * 3u + lvl;
+  const uint32_t lvl = delay <= 0 ? 0u : (delay <= (int64_t)avail * m.dec.delay_thr ? 1u : 2u);
+  const uint32_t state = ((free_bits * (uint32_t)m.dec.K) + (uint32_t)m.tr_k[h]) * 3u + lvl;
   uint32_t amask = 1u << (na - 1);
   for (int a = 0; a < na - 1; ++a)
     if (m.act_src[sw * 8 + a] == (uint8_t)slot && ((free_bits >> m.act_dst[sw * 8 + a]) & 1u)) amask |= 1u << a;
@@ -1070,13 +1103,13 @@ SFL_FN void decide_observe(V& v, Obs& o, bool greedy) {
   o.slot = slot;
   o.state = state;
   o.amask = amask;
-  o.reward = slot_rew(s.slot[v.ix((size_t)sw * m.T + h)], v.epoch);
+  o.reward = slot_rew(s.lrn.slot[v.ix((size_t)sw * m.T + h)], v.epoch);
   o.explore = 0;
   o.action = -1;
   // epsilon-greedy: the exploratory branch needs no Q value
   if (!greedy) {
     Pcg64 g = v.rng_load();
-    const double eps = v.eps_of(s.counts[v.ix(sw)]);
+    const double eps = v.eps_of(s.lrn.counts[v.ix(sw)]);
     if (pcg_double(g) < eps) {
       o.explore = 1;
       const uint32_t sub_seed = pcg_bounded(g, 2147483646u);
@@ -1158,7 +1191,7 @@ SFL_FN void decide_apply(V& v, const Obs& o, int action, Decision& d) {
   const int32_t cur = v.now - m.tr_la[h] + v.dist(h, pc, pd);
   const int32_t diff = s.tr_delay[v.ix(h)] - cur;
   const int32_t r_new = (pl_front(p) == A_STOP && !all_blocked) ? diff - 1300 : diff;
-  uint64_t& sl = s.slot[v.ix((size_t)next_sw * m.T + h)];
+  uint64_t& sl = s.lrn.slot[v.ix((size_t)next_sw * m.T + h)];
   sl = slot_make(slot_pend(sl, v.epoch), r_new, v.epoch);
   s.tr_delay[v.ix(h)] = cur;
 
@@ -1207,7 +1240,7 @@ template <class V, class Q>
 SFL_FN void env_post(V& v, const Decision& d, Q& q) {
   const SflMap& m = v.m;
   const SflState& s = v.s;
-  uint64_t& here = s.slot[v.ix((size_t)d.sw * m.T + d.h)];
+  uint64_t& here = s.lrn.slot[v.ix((size_t)d.sw * m.T + d.h)];
   const uint32_t pend = slot_pend(here, v.epoch);
   if (pend != PEND_NONE) {
     const int ps = (int)(pend & 0xFFFu);
@@ -1215,18 +1248,18 @@ SFL_FN void env_post(V& v, const Decision& d, Q& q) {
     const uint32_t pstate = (pend >> 14) & 0x3FFFu;
     const int pj = (int)((pend >> 28) & 3u);
     q.touch(ps, pslot, pstate);
-    const double lr = v.lr_of(s.counts[v.ix(ps)], v.err);
+    const double lr = v.lr_of(s.lrn.counts[v.ix(ps)], v.err);
     const double r = (double)d.reward;
     if (d.sw != ps) {
       q.touch(d.sw, d.slot, d.state);
       const double mq = q.row_max_of(d);
-      q.update(ps, pslot, pstate, pj, lr, r + m.gamma * mq, 0);
+      q.update(ps, pslot, pstate, pj, lr, r + m.upd.gamma * mq, 0);
     } else {
       q.update(ps, pslot, pstate, pj, lr, r, 0);
     }
     here = slot_make(PEND_NONE, slot_rew(here, v.epoch), v.epoch);
   }
-  uint64_t& nxt = s.slot[v.ix((size_t)d.next_sw * m.T + d.h)];
+  uint64_t& nxt = s.lrn.slot[v.ix((size_t)d.next_sw * m.T + d.h)];
   nxt = slot_make(pend_make((uint32_t)d.sw, (uint32_t)d.slot, d.state, (uint32_t)d.j), slot_rew(nxt, v.epoch), v.epoch);
   // destination bonus for newly arrived trains (distr_q.py:344-356)
   int stage = 1;
@@ -1238,8 +1271,8 @@ SFL_FN void env_post(V& v, const Decision& d, Q& q) {
     while (fresh) {
       const int tr = w * 32 + ctz32(fresh);
       fresh &= fresh - 1u;
-      for (int sw2 = 0; sw2 < m.S; ++sw2) {
-        uint64_t& sl = s.slot[v.ix((size_t)sw2 * m.T + tr)];
+      for (int sw2 = 0; sw2 < m.lrn.S; ++sw2) {
+        uint64_t& sl = s.lrn.slot[v.ix((size_t)sw2 * m.T + tr)];
         const uint32_t pe = slot_pend(sl, v.epoch);
         if (pe == PEND_NONE) continue;
         const int ps = (int)(pe & 0xFFFu);
@@ -1247,14 +1280,14 @@ SFL_FN void env_post(V& v, const Decision& d, Q& q) {
         const uint32_t pstate = (pe >> 14) & 0x3FFFu;
         const int pj = (int)((pe >> 28) & 3u);
         q.touch(ps, pslot, pstate);
-        const double lr = v.lr_of(s.counts[v.ix(ps)], v.err);
-        q.update(ps, pslot, pstate, pj, lr, 1000.0 + m.gamma * 0.0, stage);
+        const double lr = v.lr_of(s.lrn.counts[v.ix(ps)], v.err);
+        q.update(ps, pslot, pstate, pj, lr, 1000.0 + m.upd.gamma * 0.0, stage);
         sl = slot_make(PEND_NONE, slot_rew(sl, v.epoch), v.epoch);
       }
       ++stage;
     }
   }
-  s.counts[v.ix(d.sw)] += 1u;
+  s.lrn.counts[v.ix(d.sw)] += 1u;
 }
 
 template <class V>

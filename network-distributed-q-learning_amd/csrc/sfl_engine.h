@@ -145,8 +145,8 @@ struct Handle {
     float x_last_ms = 0.f;
     double x_total_ms = 0.0;
   } cv;
-  // policy-bank evaluation (sfl_create_eval / sfl_bank_*; sfl_eval.h): on an evaluation handle st.q and
-  // st.touched are null and map.bank_q / map.bank_policy point at q / policy below.  set[p]: table p was filled;
+  // policy-bank evaluation (sfl_create_eval / sfl_bank_*; sfl_eval.h): on an evaluation handle st.lrn.q and
+  // st.lrn.touched are null and map.bank_q / map.bank_policy point at q / policy below.  set[p]: table p was filled;
   // the per-env outputs of the last episode launch ([E], delays and at_dest [T][E]) and the cells the fold made of them
   struct Bank {
     bool on = false;
@@ -369,28 +369,29 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
   m.HW = md->H * md->W;
   m.cell_bits = 1;
   while ((1 << m.cell_bits) < m.HW) ++m.cell_bits;
-  m.S = md->S;
+  m.lrn.S = md->S;
   m.T = md->T;
-  m.K = md->K;
+  m.lrn.ST = md->S * md->T;
+  m.dec.K = md->K;
   m.NP = (int32_t)NP;
   m.max_episode_steps = md->max_episode_steps;
   m.mf_rate = md->mf_rate;
   m.mf_min = md->mf_min;
   m.mf_max = md->mf_max;
   mf_prepare(m);  // (mf_propose's integer forms of u < mf_rate and of the duration's modulo)
-  m.delay_thr = md->delay_threshold;
-  m.gamma = hp->gamma;
+  m.dec.delay_thr = md->delay_threshold;
+  m.upd.gamma = hp->gamma;
   m.eps0 = hp->epsilon;
   m.eps_decay = hp->epsilon_decay_rate;
   // (log2 of 0 is -inf and of a negative value NaN: the device test is then never certain and takes the table)
-  m.lr0 = hp->lr;
-  m.lr_decay = hp->lr_decay_rate;
-  m.default_q = hp->default_q;
+  m.upd.lr0 = hp->lr;
+  m.upd.lr_decay = hp->lr_decay_rate;
+  m.dec.default_q = hp->default_q;
   m.max_steps = hp->max_steps;
-  m.ntab = hp->ntab;
-  m.q_per_env = md->q_per_env;
+  m.lrn.ntab = hp->ntab;
+  m.lrn.q_per_env = md->q_per_env;
   m.rows_per_env = md->rows_per_env;
-  m.touched_words = (md->rows_per_env + 31u) / 32u;
+  m.lrn.touched_words = (md->rows_per_env + 31u) / 32u;
   m.grid = h->upload(md->grid, HW);
   m.cell_sw = h->upload(md->cell_sw, HW);
   m.sw_np = h->upload(md->sw_np, S);
@@ -419,8 +420,8 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
   m.tr_init_delay = h->upload(md->tr_init_delay, T);
   m.tr_init_dir = h->upload(md->tr_init_dir, T);
   m.tr_init_port = h->upload(md->tr_init_port, T);
-  m.eps_tab = h->upload(hp->eps_tab, (size_t)hp->ntab);
-  m.lr_tab = h->upload(hp->lr_tab, (size_t)hp->ntab);
+  m.dec.eps_tab = h->upload(hp->eps_tab, (size_t)hp->ntab);
+  m.lrn.lr_tab = h->upload(hp->lr_tab, (size_t)hp->ntab);
   {
     // the observation vector's coordinates (observer.py:303-306: the switch cell, the target station's cell): the
     // switch of a cell is cell_sw, every station is some train's target (compiler.py builds the stations from them)
@@ -543,7 +544,7 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
     m.move2c_tab = h->upload(h->keep.back().data(), h->keep.back().size());
     h->keep.push_back(std::move(ptr_));
     m.port_tr = h->upload(h->keep.back().data(), h->keep.back().size());
-    m.seedseq32 = h->be.seedseq_table();
+    m.dec.seedseq32 = h->be.seedseq_table();
     h->keep.emplace_back(trp.begin(), trp.end());
     m.tr_pack = (const int32_t*)h->upload(h->keep.back().data(), h->keep.back().size());
   }
@@ -583,18 +584,18 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
   s.occ = h->template dalloc<uint8_t>(HW * E);
   s.claim = h->template dalloc<uint8_t>(HW * E);
   s.sem = h->template dalloc<uint64_t>(NP * E);
-  s.slot = h->template dalloc<uint64_t>(S * T * E);
-  s.counts = h->template dalloc<uint32_t>(S * E);
+  s.lrn.slot = h->template dalloc<uint64_t>(S * T * E);
+  s.lrn.counts = h->template dalloc<uint32_t>(S * E);
   typename Handle<B>::Bank& bk = h->bank;
   bk.on = n_policies > 0;
   if (!bk.on) {
-    s.q = h->template dalloc<double>((size_t)m.q_per_env * E);
-    s.touched = h->template dalloc<uint32_t>((size_t)m.touched_words * E);
+    s.lrn.q = h->template dalloc<double>((size_t)m.lrn.q_per_env * E);
+    s.lrn.touched = h->template dalloc<uint32_t>((size_t)m.lrn.touched_words * E);
   } else {
     bk.P = n_policies;
     bk.set.assign(n_policies, 0);
-    bk.q = h->template dalloc<double>((size_t)m.q_per_env * n_policies);
-    bk.keys = h->template dalloc<uint32_t>((size_t)m.touched_words * n_policies);
+    bk.q = h->template dalloc<double>((size_t)m.lrn.q_per_env * n_policies);
+    bk.keys = h->template dalloc<uint32_t>((size_t)m.lrn.touched_words * n_policies);
     bk.policy = h->template dalloc<uint32_t>(E);
     bk.cum = h->template dalloc<double>(E);
     bk.arrived = h->template dalloc<int32_t>(E);
@@ -625,7 +626,7 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
       delete h;
       return fail(fn + ": device allocation failed");
     }
-  if (!m.grid || (!bk.on && !s.q) || (bk.on && !bk.q)) {
+  if (!m.grid || (!bk.on && !s.lrn.q) || (bk.on && !bk.q)) {
     delete h;
     return fail(fn + ": device allocation failed (out of memory?)");
   }
@@ -663,15 +664,15 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
   h->be.memset(s.occ, 0xFF, HW * E);
   h->be.memset(s.claim, 0xFF, HW * E);
   h->be.memset(s.sem, 0, NP * E * 8);
-  h->be.memset(s.slot, 0, S * T * E * 8);
-  h->be.memset(s.counts, 0, S * E * 4);
+  h->be.memset(s.lrn.slot, 0, S * T * E * 8);
+  h->be.memset(s.lrn.counts, 0, S * E * 4);
   h->be.memset(h->d_phase, 0, 8 * 8);
   if (!bk.on) {
-    h->be.memset(s.touched, 0, (size_t)m.touched_words * E * 4);
-    h->be.fill_f64(s.q, m.default_q, (size_t)m.q_per_env * E);
+    h->be.memset(s.lrn.touched, 0, (size_t)m.lrn.touched_words * E * 4);
+    h->be.fill_f64(s.lrn.q, m.dec.default_q, (size_t)m.lrn.q_per_env * E);
   } else {
-    h->be.memset(bk.keys, 0, (size_t)m.touched_words * bk.P * 4);
-    h->be.fill_f64(bk.q, m.default_q, (size_t)m.q_per_env * bk.P);
+    h->be.memset(bk.keys, 0, (size_t)m.lrn.touched_words * bk.P * 4);
+    h->be.fill_f64(bk.q, m.dec.default_q, (size_t)m.lrn.q_per_env * bk.P);
     h->be.memset(bk.policy, 0, E * 4);
   }
   h->seeds.assign(env_seeds, env_seeds + E);
@@ -716,7 +717,7 @@ int set_hparam_groups(Handle<B>* h, int32_t n_groups, const sfl_hparam_group* gr
   if (n_groups < 0 || n_groups > SFL_MAX_HPARAM_GROUPS)
     return fail("sfl_set_hparam_groups: n_groups outside [0, " + std::to_string(SFL_MAX_HPARAM_GROUPS) + "]");
   SflMap& m = h->map;
-  const size_t ntab = m.ntab > 0 ? (size_t)m.ntab : 0, G = (size_t)n_groups, E = h->E;
+  const size_t ntab = m.lrn.ntab > 0 ? (size_t)m.lrn.ntab : 0, G = (size_t)n_groups, E = h->E;
   const double *d_eps = nullptr, *d_lr = nullptr, *d_sc = nullptr;
   const uint16_t* d_eg = nullptr;
   if (n_groups > 0) {
@@ -780,7 +781,7 @@ int learn_begin(Handle<B>* h, const uint64_t* rng_states) {
   for (size_t e = 0; e < E; ++e)
     for (int k = 0; k < 5; ++k) soa[k * E + e] = rng_states[e * 5 + k];
   h->be.h2d(h->st.rng, soa.data(), soa.size() * 8);
-  h->be.memset(h->st.counts, 0, (size_t)h->map.S * E * 4);
+  h->be.memset(h->st.lrn.counts, 0, (size_t)h->map.lrn.S * E * 4);
   h->be.memset(h->st.ep_t, 0, E * 4);
   // every env starts the learn() call with a fresh reset, and no exploit round done yet
   std::vector<int32_t> ph(E, PH_RESET);
@@ -1021,8 +1022,8 @@ template <class B>
 int bank_set(Handle<B>* h, uint32_t p, const double* q, const uint32_t* touched) {
   if (int rc = bank_check(h, "sfl_bank_set", p)) return rc;
   const SflMap& m = h->map;
-  if (q) h->be.h2d(h->bank.q + (size_t)p * m.q_per_env, q, m.q_per_env * 8);
-  if (touched) h->be.h2d(h->bank.keys + (size_t)p * m.touched_words, touched, (size_t)m.touched_words * 4);
+  if (q) h->be.h2d(h->bank.q + (size_t)p * m.lrn.q_per_env, q, m.lrn.q_per_env * 8);
+  if (touched) h->be.h2d(h->bank.keys + (size_t)p * m.lrn.touched_words, touched, (size_t)m.lrn.touched_words * 4);
   if (h->be.sync()) return fail(h->be.error());
   h->bank.set[p] = 1;
   return 0;
@@ -1032,8 +1033,8 @@ template <class B>
 int bank_get(Handle<B>* h, uint32_t p, double* q, uint32_t* touched) {
   if (int rc = bank_check(h, "sfl_bank_get", p)) return rc;
   const SflMap& m = h->map;
-  if (q) h->be.d2h(q, h->bank.q + (size_t)p * m.q_per_env, m.q_per_env * 8);
-  if (touched) h->be.d2h(touched, h->bank.keys + (size_t)p * m.touched_words, (size_t)m.touched_words * 4);
+  if (q) h->be.d2h(q, h->bank.q + (size_t)p * m.lrn.q_per_env, m.lrn.q_per_env * 8);
+  if (touched) h->be.d2h(touched, h->bank.keys + (size_t)p * m.lrn.touched_words, (size_t)m.lrn.touched_words * 4);
   return h->be.sync() ? fail(h->be.error()) : 0;
 }
 
@@ -1048,28 +1049,28 @@ int bank_copy(Handle<B>* h, uint32_t p, Handle<B>* src, int32_t kind, uint32_t i
     return fail("sfl_bank_copy: the source is on device " + std::to_string(src->device) + ", the bank on device " +
                 std::to_string(h->device));
   const SflMap &m = h->map, &sm = src->map;
-  if (sm.q_per_env != m.q_per_env || sm.rows_per_env != m.rows_per_env)
-    return fail("sfl_bank_copy: the source's Q layout differs (q_per_env " + std::to_string(sm.q_per_env) + " / " +
-                std::to_string(m.q_per_env) + ", rows_per_env " + std::to_string(sm.rows_per_env) + " / " +
+  if (sm.lrn.q_per_env != m.lrn.q_per_env || sm.rows_per_env != m.rows_per_env)
+    return fail("sfl_bank_copy: the source's Q layout differs (q_per_env " + std::to_string(sm.lrn.q_per_env) + " / " +
+                std::to_string(m.lrn.q_per_env) + ", rows_per_env " + std::to_string(sm.rows_per_env) + " / " +
                 std::to_string(m.rows_per_env) + "): another map");
-  if (memcmp(&sm.default_q, &m.default_q, 8) != 0) return fail("sfl_bank_copy: the source's default_q differs");
+  if (memcmp(&sm.dec.default_q, &m.dec.default_q, 8) != 0) return fail("sfl_bank_copy: the source's default_q differs");
   const double* q = nullptr;
   const uint32_t* keys = nullptr;
   if (kind == SFL_BANK_FROM_ENV) {
     if (index >= src->E) return fail("sfl_bank_copy: env " + std::to_string(index) + " of " + std::to_string(src->E));
-    q = src->st.q + (size_t)index * m.q_per_env;
-    keys = src->st.touched + (size_t)index * m.touched_words;
+    q = src->st.lrn.q + (size_t)index * m.lrn.q_per_env;
+    keys = src->st.lrn.touched + (size_t)index * m.lrn.touched_words;
   } else if (kind == SFL_BANK_FROM_COHORT) {
     if (index >= src->cons_n)
       return fail("sfl_bank_copy: no consensus cohort " + std::to_string(index) + " (the source's last sfl_consensus made " +
                   std::to_string(src->cons_n) + ")");
-    q = src->cons_q + (size_t)index * m.q_per_env;
-    keys = src->cons_keys + (size_t)index * m.touched_words;
+    q = src->cons_q + (size_t)index * m.lrn.q_per_env;
+    keys = src->cons_keys + (size_t)index * m.lrn.touched_words;
   } else {
     return fail("sfl_bank_copy: kind " + std::to_string(kind) + " (SFL_BANK_FROM_ENV or SFL_BANK_FROM_COHORT)");
   }
-  h->be.d2d(h->bank.q + (size_t)p * m.q_per_env, q, m.q_per_env * 8);
-  h->be.d2d(h->bank.keys + (size_t)p * m.touched_words, keys, (size_t)m.touched_words * 4);
+  h->be.d2d(h->bank.q + (size_t)p * m.lrn.q_per_env, q, m.lrn.q_per_env * 8);
+  h->be.d2d(h->bank.keys + (size_t)p * m.lrn.touched_words, keys, (size_t)m.lrn.touched_words * 4);
   if (h->be.sync()) return fail(std::string("sfl_bank_copy: ") + h->be.error());
   h->bank.set[p] = 1;
   return 0;
@@ -1260,8 +1261,8 @@ int trans_begin(Handle<B>* h, const sfl_env_trans_io* io) {
                 "cannot hold it)");
   if (((uintptr_t)io->obs & 7u) || ((uintptr_t)io->next_obs & 7u) || ((uintptr_t)io->next_action_mask & 15u))
     return fail(std::string(fn) + "obs and next_obs must be 8-byte and next_action_mask 16-byte aligned");
-  if (h->map.S > 0xFFFF) return fail(std::string(fn) + "more than 65,535 switches");
-  const size_t E = h->E, T = h->map.T, S = h->map.S;
+  if (h->map.lrn.S > 0xFFFF) return fail(std::string(fn) + "more than 65,535 switches");
+  const size_t E = h->E, T = h->map.T, S = h->map.lrn.S;
   const size_t nb = (E + TRANS_BLOCK - 1) / TRANS_BLOCK;
   TransArgs& a = h->tr.a;
   if (!a.tab) {
@@ -1280,9 +1281,9 @@ int trans_begin(Handle<B>* h, const sfl_env_trans_io* io) {
   }
   a.E = h->E;
   a.N = io->capacity;
-  a.S = h->map.S;
+  a.S = h->map.lrn.S;
   a.T = h->map.T;
-  a.K = h->map.K;
+  a.K = h->map.dec.K;
   a.sw_np = h->map.sw_np;
   a.sw_na = h->map.sw_na;
   a.sw_rc = h->d_sw_rc;
@@ -1363,7 +1364,7 @@ int env_begin(Handle<B>* h, bool wave = false) {
       return fail(fn + ": the handle has no wave shape (" +
                   (h->variant_note.empty() ? std::string("SFL_KERNEL=scalar") : h->variant_note) + ")");
   }
-  const size_t E = h->E, T = h->map.T, S = h->map.S, NP = h->map.NP;
+  const size_t E = h->E, T = h->map.T, S = h->map.lrn.S, NP = h->map.NP;
   if (!h->d_ext) {
     SflExt& x = h->ext;
     x.actions = h->template dalloc<int32_t>(E);
@@ -1410,7 +1411,7 @@ int env_begin(Handle<B>* h, bool wave = false) {
   h->be.memset(st.occ, 0xFF, (size_t)h->map.HW * E);
   h->be.memset(st.claim, 0xFF, (size_t)h->map.HW * E);
   h->be.memset(st.sem, 0, NP * E * 8);
-  h->be.memset(st.slot, 0, S * T * E * 8);
+  h->be.memset(st.lrn.slot, 0, S * T * E * 8);
   h->be.memset(st.step_ctr, 0, E * 8);
   std::vector<int32_t> none(E, -1);
   h->be.h2d((void*)h->ext.actions, none.data(), E * 4);
@@ -1491,7 +1492,7 @@ int env_step_dev(Handle<B>* h, const sfl_env_dev_io* dio) {
   x.truncated = io.truncated ? io.truncated : own.truncated;
   SflEnc enc{};
   enc.E = h->E;
-  enc.K = h->map.K;
+  enc.K = h->map.dec.K;
   enc.agent = x.agent;
   enc.slot = x.slot;
   enc.state = x.state;
@@ -1528,8 +1529,8 @@ int env_sync(Handle<B>* h) {
 
 template <class B>
 int get_obs_tables(Handle<B>* h, int32_t* switch_rc, int32_t* station_rc) {
-  if (switch_rc) h->be.d2h(switch_rc, h->d_sw_rc, (size_t)h->map.S * 8);
-  if (station_rc) h->be.d2h(station_rc, h->d_st_rc, (size_t)h->map.K * 8);
+  if (switch_rc) h->be.d2h(switch_rc, h->d_sw_rc, (size_t)h->map.lrn.S * 8);
+  if (station_rc) h->be.d2h(station_rc, h->d_st_rc, (size_t)h->map.dec.K * 8);
   return h->be.sync() ? fail(h->be.error()) : 0;
 }
 
@@ -1555,7 +1556,7 @@ int part_config(Handle<B>* h, int rank, int world, const int32_t* owner, uint32_
   // segments must hold every env's staged records
   const uint32_t upd_env = cap_upd / h->E < PART_UPD_ENV_MAX ? cap_upd / h->E : PART_UPD_ENV_MAX;
   if (upd_env < 2) return fail("sfl_part_config: update capacity must allow two records per local env");
-  const int S = h->map.S, K = h->map.K;
+  const int S = h->map.lrn.S, K = h->map.dec.K;
   std::vector<int32_t> own(owner, owner + S);
   for (int s = 0; s < S; ++s)
     if (own[s] < 0 || own[s] >= world) return fail("sfl_part_config: owner out of range");
@@ -1577,10 +1578,10 @@ int part_config(Handle<B>* h, int rank, int world, const int32_t* owner, uint32_
   }
   // the env-local Q-table is not used in this mode: release it before the owned tables
   h->be.sync();
-  h->dfree(h->st.q);
-  h->dfree(h->st.touched);
-  h->st.q = nullptr;
-  h->st.touched = nullptr;
+  h->dfree(h->st.lrn.q);
+  h->dfree(h->st.lrn.touched);
+  h->st.lrn.q = nullptr;
+  h->st.lrn.touched = nullptr;
   SflPart& P = h->part;
   P.rank = rank;
   P.world = world;
@@ -1621,11 +1622,11 @@ int part_config(Handle<B>* h, int rank, int world, const int32_t* owner, uint32_
   h->be.memset(P.cnt, 0, ((size_t)world + 4) * 4);
   h->be.memset(P.sums, 0, 4 * 8);
   h->be.memset(P.cnt_out, 0, (4 + ((size_t)PART_NCNT(world) + 1) / 2) * 8);
-  h->be.fill_f64(P.q_own, h->map.default_q, (size_t)E_tot * off);
+  h->be.fill_f64(P.q_own, h->map.dec.default_q, (size_t)E_tot * off);
   h->be.memset(P.touched_own, 0, (size_t)E_tot * P.own_words * 4);
   h->be.memset(P.dec_done, 0, h->E * 8);
   // a grouped shape (G < 64) becomes its one-env-per-wavefront shape: same env-major state layout
-  if (h->variant > 0 && kVariants[h->variant].G != 64) h->variant = wave64_variant(h->map.S, h->map.T);
+  if (h->variant > 0 && kVariants[h->variant].G != 64) h->variant = wave64_variant(h->map.lrn.S, h->map.T);
   if (h->variant > 0) {  // the wave kernels keep each env's scalars in a block between rounds
     P.eblk = h->template dalloc<uint32_t>((size_t)h->E * PART_EB);
     if (!P.eblk) return fail("sfl_part_config: allocation failed (out of memory?)");
@@ -1641,16 +1642,16 @@ template <class B>
 int part_qinit(Handle<B>* h, uint32_t n_rows, const uint32_t* row_port, const uint32_t* row_state, const double* values) {
   SflPart& P = h->part;
   const int rank = P.rank;
-  std::vector<int32_t> own(h->map.S);
+  std::vector<int32_t> own(h->map.lrn.S);
   h->be.d2h(own.data(), P.owner, own.size() * 4);
   if (h->be.sync()) return fail(h->be.error());
   // apply on the host copy of one env's owned table, then replicate over all envs
-  std::vector<uint64_t> qo(4 * (size_t)h->map.S);
-  std::vector<uint32_t> ro(4 * (size_t)h->map.S);
+  std::vector<uint64_t> qo(4 * (size_t)h->map.lrn.S);
+  std::vector<uint32_t> ro(4 * (size_t)h->map.lrn.S);
   h->be.d2h(qo.data(), P.q_off_own, qo.size() * 8);
   h->be.d2h(ro.data(), P.row_own, ro.size() * 4);
   if (h->be.sync()) return fail(h->be.error());
-  std::vector<double> tab(P.q_own_per_env, h->map.default_q);
+  std::vector<double> tab(P.q_own_per_env, h->map.dec.default_q);
   std::vector<uint32_t> bits(P.own_words, 0u);
   for (uint32_t r = 0; r < n_rows; ++r) {
     const uint32_t g = row_port[r], st = row_state[r];
@@ -1658,7 +1659,7 @@ int part_qinit(Handle<B>* h, uint32_t n_rows, const uint32_t* row_port, const ui
     const int w = h->h_q_w[g];
     for (int j = 0; j < w; ++j) {
       const double v = values[(size_t)r * 4 + j];
-      tab[qo[g] + (size_t)st * w + j] = (v != v) ? h->map.default_q : v;
+      tab[qo[g] + (size_t)st * w + j] = (v != v) ? h->map.dec.default_q : v;
     }
     const uint32_t rid = ro[g] + st;
     bits[rid >> 5] |= 1u << (rid & 31u);
@@ -1681,9 +1682,9 @@ template <class B>
 int part_get_q(Handle<B>* h, uint32_t genv, double* q, uint32_t* touched) {
   SflPart& P = h->part;
   if (genv >= P.E_tot) return fail("sfl_part_get_q: env out of range");
-  std::vector<int32_t> own(h->map.S);
-  std::vector<uint64_t> qo(4 * (size_t)h->map.S);
-  std::vector<uint32_t> ro(4 * (size_t)h->map.S);
+  std::vector<int32_t> own(h->map.lrn.S);
+  std::vector<uint64_t> qo(4 * (size_t)h->map.lrn.S);
+  std::vector<uint32_t> ro(4 * (size_t)h->map.lrn.S);
   std::vector<double> tab(P.q_own_per_env);
   std::vector<uint32_t> bits(P.own_words);
   h->be.d2h(own.data(), P.owner, own.size() * 4);
@@ -1692,8 +1693,8 @@ int part_get_q(Handle<B>* h, uint32_t genv, double* q, uint32_t* touched) {
   if (P.q_own_per_env) h->be.d2h(tab.data(), P.q_own + (size_t)genv * P.q_own_per_env, tab.size() * 8);
   if (P.own_words) h->be.d2h(bits.data(), P.touched_own + (size_t)genv * P.own_words, bits.size() * 4);
   if (h->be.sync()) return fail(h->be.error());
-  const int K = h->map.K;
-  for (int s = 0; s < h->map.S; ++s) {
+  const int K = h->map.dec.K;
+  for (int s = 0; s < h->map.lrn.S; ++s) {
     if (own[s] != P.rank) continue;
     const int np = h->h_sw_np[s];
     for (int i = 0; i < np; ++i) {
@@ -1818,7 +1819,7 @@ template <class B>
 int part_set_local_rows(Handle<B>* h, const uint8_t* local) {
   SflPart& P = h->part;
   if (!P.world) return fail("sfl_part_set_local_rows: handle not partitioned");
-  const int S = h->map.S;
+  const int S = h->map.lrn.S;
   std::vector<int32_t> own(S);
   h->be.d2h(own.data(), P.owner, own.size() * 4);
   if (h->be.sync()) return fail(h->be.error());
@@ -1870,15 +1871,15 @@ int consensus(Handle<B>* h, int32_t mode, uint32_t flags, uint32_t n_cohorts, co
         return fail("sfl_consensus: env " + std::to_string(e) + " is in cohort " + std::to_string(env_cohort[e]) + " of " +
                     std::to_string(n_cohorts));
   const SflMap& m = h->map;
-  const uint64_t Q = m.q_per_env;
-  const uint32_t tw = m.touched_words;
+  const uint64_t Q = m.lrn.q_per_env;
+  const uint32_t tw = m.lrn.touched_words;
   if (!h->d_cell_row) {
     // each cell's row id, as k_qinit derives it: block g holds rows row_base[g] + state, q_w[g] cells each
     std::vector<uint32_t> cr(Q ? Q : 1, CONS_NO_ROW);
-    for (int s = 0; s < m.S; ++s)
+    for (int s = 0; s < m.lrn.S; ++s)
       for (int i = 0; i < (int)h->h_sw_np[s]; ++i) {
         const size_t g = (size_t)s * 4 + i;
-        const uint64_t w = h->h_q_w[g], nrows = ((uint64_t)1 << h->h_sw_np[s]) * (uint64_t)m.K * 3u;
+        const uint64_t w = h->h_q_w[g], nrows = ((uint64_t)1 << h->h_sw_np[s]) * (uint64_t)m.dec.K * 3u;
         if (w == 0) continue;
         if (h->h_q_off[g] + nrows * w > Q || h->h_row_base[g] + nrows > m.rows_per_env)
           return fail("sfl_consensus: a Q block lies outside the env's table (map compiler mismatch)");
@@ -1947,11 +1948,11 @@ int consensus(Handle<B>* h, int32_t mode, uint32_t flags, uint32_t n_cohorts, co
   a.n_combos = (uint32_t)combos.size();
   a.n_slots = n_slots;
   a.Q = Q;
-  a.default_bits = cons_bits(m.default_q);
+  a.default_bits = cons_bits(m.dec.default_q);
   const uint64_t q_tiles = (Q + CONS_TILE - 1) / CONS_TILE;
   a.cells_cap = q_tiles * CONS_TILE;
-  a.q = h->st.q;
-  a.touched = h->st.touched;
+  a.q = h->st.lrn.q;
+  a.touched = h->st.lrn.touched;
   a.cell_row = h->d_cell_row;
   a.cons_q = h->cons_q;
   a.cons_keys = h->cons_keys;
@@ -1993,7 +1994,7 @@ int get_consensus_q(Handle<B>* h, uint32_t cohort, double* q, uint32_t* touched)
   if (!h->cons_n) return fail("sfl_get_consensus_q: no sfl_consensus call yet");
   if (cohort >= h->cons_n)
     return fail("sfl_get_consensus_q: cohort " + std::to_string(cohort) + " of " + std::to_string(h->cons_n));
-  const size_t Q = h->map.q_per_env, tw = h->map.touched_words;
+  const size_t Q = h->map.lrn.q_per_env, tw = h->map.lrn.touched_words;
   if (q) h->be.d2h(q, h->cons_q + (size_t)cohort * Q, Q * 8);
   if (touched) h->be.d2h(touched, h->cons_keys + (size_t)cohort * tw, tw * 4);
   return h->be.sync() ? fail(h->be.error()) : 0;
@@ -2241,7 +2242,7 @@ template <class B>
 uint32_t snap_fields(Handle<B>* h, SnapField* f, uint32_t* n_fields, uint32_t* seed_off) {
   const SflState& s = h->st;
   const SflMap& m = h->map;
-  const uint32_t T = (uint32_t)m.T, S = (uint32_t)m.S, NP = (uint32_t)m.NP, HW = (uint32_t)m.HW;
+  const uint32_t T = (uint32_t)m.T, S = (uint32_t)m.lrn.S, NP = (uint32_t)m.NP, HW = (uint32_t)m.HW;
   const uint32_t wave = h->variant > 0 ? 1u : 0u;
   uint32_t n = 0, off = 0;
   auto add = [&](void* base, uint32_t elem, uint32_t count, uint32_t major) {
@@ -2284,8 +2285,8 @@ uint32_t snap_fields(Handle<B>* h, SnapField* f, uint32_t* n_fields, uint32_t* s
   add(s.claim, 1, HW, 0);
   if (wave) add(s.sem, 4, NP, 1);  // (32-bit records [E][NP] in the array sized for the 64-bit ones)
   else add(s.sem, 8, NP, 0);
-  add(s.slot, 8, S * T, wave);
-  add(s.counts, 4, S, wave);
+  add(s.lrn.slot, 8, S * T, wave);
+  add(s.lrn.counts, 4, S, wave);
   static_assert(SNAP_MAX_FIELDS >= 35, "fields");
   *n_fields = n;
   return (off + 7u) / 8u * 8u;
@@ -2295,9 +2296,9 @@ template <class B>
 uint64_t snap_fingerprint(Handle<B>* h) {
   const SflMap& m = h->map;
   uint64_t fp = snap_hash(0xCBF29CE484222325ull, &h->snap.map_fp, 8);
-  fp = snap_hash(fp, &m.gamma, 8);
-  fp = snap_hash(fp, &m.default_q, 8);
-  const int64_t sc[] = {m.ntab, m.max_steps, m.delay_thr, m.mf_steps > 0 ? 1 : 0, h->variant > 0 ? 1 : 0};
+  fp = snap_hash(fp, &m.upd.gamma, 8);
+  fp = snap_hash(fp, &m.dec.default_q, 8);
+  const int64_t sc[] = {m.lrn.ntab, m.max_steps, m.dec.delay_thr, m.mf_steps > 0 ? 1 : 0, h->variant > 0 ? 1 : 0};
   return snap_hash(fp, sc, sizeof sc);
 }
 
@@ -2306,7 +2307,7 @@ int snap_refuse(Handle<B>* h, const std::string& fn) {
   if (h->bank.on) return fail(fn + ": an evaluation handle has no per-env table (sfl_create_eval)");
   if (h->part.world) return fail(fn + ": the handle is graph-partitioned (its tables are owned rows)");
   if (h->env_mode) return fail(fn + ": the handle is in external-action mode (no learner)");
-  if (h->map.q_per_env >= (1ull << 32)) return fail(fn + ": Q-table beyond 2^32 cells per env");
+  if (h->map.lrn.q_per_env >= (1ull << 32)) return fail(fn + ": Q-table beyond 2^32 cells per env");
   return 0;
 }
 
@@ -2319,12 +2320,12 @@ int snap_tables(Handle<B>* h, const std::string& fn) {
   const uint32_t rows = m.rows_per_env;
   sn.row_w.assign(rows ? rows : 1, 0);
   sn.row_cell.assign(rows ? rows : 1, 0);
-  for (int s = 0; s < m.S; ++s)
+  for (int s = 0; s < m.lrn.S; ++s)
     for (int i = 0; i < (int)h->h_sw_np[s]; ++i) {
       const size_t g = (size_t)s * 4 + i;
-      const uint64_t w = h->h_q_w[g], nrows = ((uint64_t)1 << h->h_sw_np[s]) * (uint64_t)m.K * 3u;
+      const uint64_t w = h->h_q_w[g], nrows = ((uint64_t)1 << h->h_sw_np[s]) * (uint64_t)m.dec.K * 3u;
       if (w == 0) continue;
-      if (w > 4 || h->h_q_off[g] + nrows * w > m.q_per_env || h->h_row_base[g] + nrows > rows)
+      if (w > 4 || h->h_q_off[g] + nrows * w > m.lrn.q_per_env || h->h_row_base[g] + nrows > rows)
         return fail(fn + ": a Q block lies outside the env's table (map compiler mismatch)");
       for (uint64_t r = 0; r < nrows; ++r) {
         sn.row_w[h->h_row_base[g] + r] = (uint8_t)w;
@@ -2356,15 +2357,15 @@ void snap_args(Handle<B>* h, SnapArgs& a, uint32_t n) {
   a = SnapArgs{};
   a.E = h->E;
   a.n = n;
-  a.tw = m.touched_words;
+  a.tw = m.lrn.touched_words;
   a.rows = m.rows_per_env;
   a.groups = (m.rows_per_env + SNAP_GROUP - 1) / SNAP_GROUP;
   uint32_t seed_off = 0;
   a.state_bytes = snap_fields(h, a.fields, &a.n_fields, &seed_off);
-  a.Q = m.q_per_env;
-  a.default_bits = cons_bits(m.default_q);
-  a.q = (uint64_t*)h->st.q;
-  a.touched = h->st.touched;
+  a.Q = m.lrn.q_per_env;
+  a.default_bits = cons_bits(m.dec.default_q);
+  a.q = (uint64_t*)h->st.lrn.q;
+  a.touched = h->st.lrn.touched;
   a.row_cell = h->snap.d_row_cell;
   a.row_w = h->snap.d_row_w;
 }
@@ -2379,9 +2380,9 @@ int state_info(Handle<B>* h, sfl_state_desc* out) {
   out->state_bytes = snap_fields(h, f, &nf, &seed_off);
   out->seed_offset = seed_off;
   out->fingerprint = snap_fingerprint(h);
-  out->q_per_env = h->map.q_per_env;
+  out->q_per_env = h->map.lrn.q_per_env;
   out->layout = h->variant > 0 ? SFL_STATE_WAVE : SFL_STATE_LANE;
-  out->touched_words = h->map.touched_words;
+  out->touched_words = h->map.lrn.touched_words;
   out->rows_per_env = h->map.rows_per_env;
   return 0;
 }

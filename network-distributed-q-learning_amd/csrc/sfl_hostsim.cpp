@@ -39,13 +39,13 @@ struct HostBackend {
       for (uint32_t r = 0; r < n_rows; ++r) {
         const uint32_t g = port[r], st = state[r];
         const int w = m.q_w[g];
-        double* row = s.q + (size_t)e * m.q_per_env + m.q_off[g] + (size_t)st * w;
+        double* row = s.lrn.q + (size_t)e * m.lrn.q_per_env + m.q_off[g] + (size_t)st * w;
         for (int j = 0; j < w; ++j) {
           const double v = vals[(size_t)r * 4 + j];
-          row[j] = (v != v) ? m.default_q : v;
+          row[j] = (v != v) ? m.dec.default_q : v;
         }
         const uint32_t rid = m.row_base[g] + st;
-        s.touched[(size_t)e * m.touched_words + (rid >> 5)] |= 1u << (rid & 31u);
+        s.lrn.touched[(size_t)e * m.lrn.touched_words + (rid >> 5)] |= 1u << (rid & 31u);
       }
   }
   int run(const sfl::SflMap& m, const sfl::SflState& s, const sfl::SflCtl& c, int /*variant*/, float* ms) {

@@ -359,6 +359,15 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
   // shapes with vector table loads only: G = 64 reads the table through the scalar cache, the external-action, bank
   // and partitioned shapes keep their order
   static constexpr bool EPS_EARLY = !EXT && !BANK && !PART && G < 64 && !xp::kEpsConst && !xp::kNoRng;
+  // PHASE_BLK: decide() and post() copy the map's and the state's learner blocks (sfl_core.h MapDecide / MapLearn /
+  // MapUpdate / StateLearn) at their top and hold the copies in front of the phase's work by a scheduling barrier:
+  // the fields arrive with one or two wide scalar loads and one wait instead of a load and a wait of its own at every
+  // use (each of which also waits for whatever LDS read is in flight).  The grouped learning and bank shapes only:
+  // G = 64 and external-action mode keep every field read where it is used (Blk<T> is a reference there) -- the
+  // copies cost one-env-per-wave kernels a spilled VGPR and an external-action shape six VGPRs (scripts/kres_diff.py)
+  static constexpr bool PHASE_BLK = G < 64 && !EXT;
+  template <class T>
+  using Blk = typename std::conditional<PHASE_BLK, const T, const T&>::type;
   int pf_n = 0;  // RING: decisions since the batch was staged (= the record of the next one)
   static constexpr int kG = G;
   static_assert(TPL * G <= 128, "at most 128 train slots per env");
@@ -470,15 +479,17 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
       qb = nullptr;
       touchb = nullptr;
     } else if constexpr (BANK) {  // (G = 64: the table's base, wave-uniform; G < 64: qbase() from `pol`)
-      qb = G == 64 ? const_cast<double*>(m.bank_q) + (size_t)U(ld(m.bank_policy, (size_t)e_)) * m.q_per_env : nullptr;
+      qb = G == 64 ? const_cast<double*>(m.bank_q) + (size_t)U(ld(m.bank_policy, (size_t)e_)) * m.lrn.q_per_env : nullptr;
       touchb = nullptr;
     } else {
-      qb = s.q + (size_t)e * m.q_per_env;
-      touchb = s.touched + (size_t)e * m.touched_words;
+      qb = s.lrn.q + (size_t)e * m.lrn.q_per_env;
+      touchb = s.lrn.touched + (size_t)e * m.lrn.touched_words;
     }
-    slotb = s.slot + (size_t)e * (uint32_t)(m.S * m.T);
+    slotb = s.lrn.slot + (size_t)e * (uint32_t)m.lrn.ST;
   }
-  __device__ __forceinline__ uint32_t slot_ix(int sw, int h) const { return (uint32_t)(h * m.S + sw); }
+  // (the overloads with a MapLearn / StateLearn argument: a phase's copy of the block, see PHASE_BLK)
+  __device__ __forceinline__ uint32_t slot_ix(const MapLearn& ml, int sw, int h) const { return (uint32_t)(h * ml.S + sw); }
+  __device__ __forceinline__ uint32_t slot_ix(int sw, int h) const { return slot_ix(m.lrn, sw, h); }
 
   __device__ __forceinline__ size_t ix(size_t i) const { return i * (size_t)E + e; }
   // per-train / per-port / per-switch state between launches: env-major ([E][T], [E][NP], [E][S];
@@ -509,7 +520,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     if constexpr (PART) return LDC(P->row_own, (size_t)g);
     else return pr.row_base();
   }
-  __device__ __forceinline__ size_t cix(int sw) const { return (size_t)e * (uint32_t)m.S + (uint32_t)sw; }
+  __device__ __forceinline__ size_t cix(int sw) const { return (size_t)e * (uint32_t)m.lrn.S + (uint32_t)sw; }
 
   // ---- group primitives -------------------------------------------------------------
   // the lane index in the group, re-read (v_mbcnt) where it is used: values derived from it are then
@@ -698,7 +709,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
   }
   // cell_sw of a move's destination cell (packed in the move table when the map has <= 254 switches)
   __device__ __forceinline__ int dest_sw(const Move& mv) const {
-    if (m.S <= 254) return mv.sw == 0xFF ? -1 : mv.sw;
+    if (m.lrn.S <= 254) return mv.sw == 0xFF ? -1 : mv.sw;
     return mv.cell >= 0 ? (int)ld(m.cell_sw, (size_t)mv.cell) : -1;
   }
   // flatland-lite check_action_on_agent as a table lookup; U: wave-uniform arguments (scalar load)
@@ -839,35 +850,38 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
   // G < 64 -- half of a held pointer, and no LDS read in front of every Q address as a copy beside the env record
   // would be (the staging's Q loads are the last level of a chain of dependent loads already); the registers the
   // epsilon draw and the Q update no longer hold pay for it several times over (profiles/eval_bank_kres.txt)
-  __device__ __forceinline__ double* qbase() const {
+  __device__ __forceinline__ double* qbase(const MapLearn& ml, const StateLearn& sl) const {
     if constexpr (PART || G == 64) return qb;
-    else if constexpr (BANK) return const_cast<double*>(m.bank_q) + (size_t)pol * m.q_per_env;
-    else return s.q + (size_t)e * m.q_per_env;
+    else if constexpr (BANK) return const_cast<double*>(m.bank_q) + (size_t)pol * ml.q_per_env;
+    else return sl.q + (size_t)e * ml.q_per_env;
   }
-  __device__ __forceinline__ uint32_t* tbase() const {
+  __device__ __forceinline__ double* qbase() const { return qbase(m.lrn, s.lrn); }
+  __device__ __forceinline__ uint32_t* tbase(const MapLearn& ml, const StateLearn& sl) const {
     if constexpr (PART || G == 64) return touchb;
-    else return s.touched + (size_t)e * m.touched_words;
+    else return sl.touched + (size_t)e * ml.touched_words;
   }
-  __device__ __forceinline__ uint64_t* sbase() const {
+  __device__ __forceinline__ uint64_t* sbase(const MapLearn& ml, const StateLearn& sl) const {
     if constexpr (G == 64) return slotb;
-    else return s.slot + (size_t)e * (uint32_t)(m.S * m.T);
+    else return sl.slot + (size_t)e * (uint32_t)ml.ST;
   }
+  __device__ __forceinline__ uint64_t* sbase() const { return sbase(m.lrn, s.lrn); }
   // global-address-space atomic: a flat atomic would also count on lgkmcnt, so the decision's next
   // LDS read or scalar load would wait for its L2 round trip
-  __device__ __forceinline__ void touch_row(uint32_t row) const {
+  __device__ __forceinline__ void touch_row(const MapLearn& ml, const StateLearn& sl, uint32_t row) const {
     if constexpr (BANK) return;  // (the bank is read-only: a greedy run's key-set inserts are not recorded)
-    __hip_atomic_fetch_or((SFL_AS_G uint32_t*)tbase() + (row >> 5), 1u << (row & 31u), __ATOMIC_RELAXED,
+    __hip_atomic_fetch_or((SFL_AS_G uint32_t*)tbase(ml, sl) + (row >> 5), 1u << (row & 31u), __ATOMIC_RELAXED,
                           __HIP_MEMORY_SCOPE_AGENT);
   }
+  __device__ __forceinline__ void touch_row(uint32_t row) const { touch_row(m.lrn, s.lrn, row); }
   // HPG: the env's rows of the grouped tables, and scalar k of its group (HPG_EPS0 ...: SflMap::hpg_sc).  The
   // group is group-uniform, so G = 64 reads them with scalar loads and G < 64 with vector loads (LDC)
   __device__ __forceinline__ const double* eps_row() const {
-    if constexpr (HPG) return m.hpg_eps_tab + (size_t)hgrp * (uint32_t)m.ntab;
-    else return m.eps_tab;
+    if constexpr (HPG) return m.hpg_eps_tab + (size_t)hgrp * (uint32_t)m.lrn.ntab;
+    else return m.dec.eps_tab;
   }
   __device__ __forceinline__ const double* lr_row() const {
-    if constexpr (HPG) return m.hpg_lr_tab + (size_t)hgrp * (uint32_t)m.ntab;
-    else return m.lr_tab;
+    if constexpr (HPG) return m.hpg_lr_tab + (size_t)hgrp * (uint32_t)m.lrn.ntab;
+    else return m.lrn.lr_tab;
   }
   __device__ __forceinline__ double hsc(int k) const { return LDC(m.hpg_sc, (size_t)hgrp * 4u + (uint32_t)k); }
   __device__ __forceinline__ double eps0_() const {
@@ -883,26 +897,40 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
   // is the shortcut's without a load of the group's lr_decay per update; the group's scalars only past the table
   __device__ __forceinline__ double lr_of(uint32_t n) {
     if constexpr (HPG) {
-      if (n < (uint32_t)m.ntab) return LDC(lr_row(), (size_t)n);
+      if (n < (uint32_t)m.lrn.ntab) return LDC(lr_row(), (size_t)n);
       if (hsc(HPG_LR_DECAY) != 1.0) lerr |= E_LR_TABLE;
       return hsc(HPG_LR0);
     } else {
-      if (m.lr_decay == 1.0) return m.lr0;  // lr0 * 1.0**n (distr_q.py:70-79)
-      if (n < (uint32_t)m.ntab) return LDC(m.lr_tab, (size_t)n);
+      if (m.upd.lr_decay == 1.0) return m.upd.lr0;  // lr0 * 1.0**n (distr_q.py:70-79)
+      if (n < (uint32_t)m.lrn.ntab) return LDC(m.lrn.lr_tab, (size_t)n);
       lerr |= E_LR_TABLE;
-      return m.lr0;
+      return m.upd.lr0;
+    }
+  }
+  // post()'s form on its copies of the blocks: the interaction count (an LDS read) is fetched on the table path
+  // only -- lr_decay == 1.0 never looks at it
+  template <class F>
+  __device__ __forceinline__ double lr_of(const MapLearn& ml, const MapUpdate& mu, F&& count) {
+    if constexpr (HPG) {
+      return lr_of(count());
+    } else {
+      if (mu.lr_decay == 1.0) return mu.lr0;
+      const uint32_t n = count();
+      if (n < (uint32_t)ml.ntab) return LDC(ml.lr_tab, (size_t)n);
+      lerr |= E_LR_TABLE;
+      return mu.lr0;
     }
   }
   __device__ __forceinline__ double lr_of_var(uint32_t n) {
     if constexpr (HPG) {
-      if (n < (uint32_t)m.ntab) return ld(lr_row(), (size_t)n);
+      if (n < (uint32_t)m.lrn.ntab) return ld(lr_row(), (size_t)n);
       if (hsc(HPG_LR_DECAY) != 1.0) lerr |= E_LR_TABLE;
       return hsc(HPG_LR0);
     } else {
-      if (m.lr_decay == 1.0) return m.lr0;
-      if (n < (uint32_t)m.ntab) return ld(m.lr_tab, (size_t)n);
+      if (m.upd.lr_decay == 1.0) return m.upd.lr0;
+      if (n < (uint32_t)m.lrn.ntab) return ld(m.lrn.lr_tab, (size_t)n);
       lerr |= E_LR_TABLE;
-      return m.lr0;
+      return m.upd.lr0;
     }
   }
 
@@ -933,7 +961,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
 #pragma unroll
     for (int k = 0; k < PPL; ++k) rw[k] = ld(sem_words(), pix(k * G + lane < m.NP ? k * G + lane : 0));
 #pragma unroll
-    for (int k = 0; k < SPL; ++k) nw[k] = (EXT || BANK) ? 0u : ld(s.counts, cix(k * G + lane < m.S ? k * G + lane : 0));
+    for (int k = 0; k < SPL; ++k) nw[k] = (EXT || BANK) ? 0u : ld(s.lrn.counts, cix(k * G + lane < m.lrn.S ? k * G + lane : 0));
 #pragma unroll
     for (int k = 0; k < TPL; ++k) {
       const int hk = lane + G * k;
@@ -974,7 +1002,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     }
 #pragma unroll
     for (int k = 0; !EXT && !BANK && k < SPL; ++k) {
-      const uint32_t n = k * G + lane < m.S ? nw[k] : 0u;
+      const uint32_t n = k * G + lane < m.lrn.S ? nw[k] : 0u;
       lcnt[k * G + lane] = n;
     }
     if constexpr (PART) {
@@ -1098,7 +1126,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
 #pragma unroll
     for (int k = 0; k < SPL; ++k) {
       const int sw = k * G + lane;
-      if (!EXT && !BANK && sw < m.S && (!PART || n0[PART ? k : 0] != 0u)) st(s.counts, cix(sw), nw[k]);
+      if (!EXT && !BANK && sw < m.lrn.S && (!PART || n0[PART ? k : 0] != 0u)) st(s.lrn.counts, cix(sw), nw[k]);
     }
     uint32_t err = 0;
 #pragma unroll
@@ -1225,7 +1253,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     // new (switch, train) epoch: slots from older episodes read as empty
     epoch = (epoch + 1u) & 0xFFu;
     if (epoch == 0) {
-      for (int i = lane; i < m.S * m.T; i += G) st(sbase(), (size_t)i, slot_make(PEND_NONE, 0, 0));
+      for (int i = lane; i < m.lrn.S * m.T; i += G) st(sbase(), (size_t)i, slot_make(PEND_NONE, 0, 0));
       epoch = 1;
     }
     cum = 0;
@@ -1565,7 +1593,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
             if (st4 == S_READY || st4 == S_MOVING) sw = sw_at;
             else if ((st4 == S_STOPPED || st4 == S_MALF) && tb_prev(bits[k]) == A_STOP) sw = sw_at;
             else if (st4 == S_STOPPED || st4 == S_MALF) sw = (int)((nprv[k] & 0xFFFFu) >> 2);
-            if (sw >= m.S) {  // next port is None: the reference would raise here
+            if (sw >= m.lrn.S) {  // next port is None: the reference would raise here
               lerr |= E_PORT;
             } else if (sw >= 0) {
               act[k] = true;
@@ -1741,8 +1769,8 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     }
     const int32_t dl = now - la + dd;
     const int32_t avail = la - (int32_t)trw[0];
-    const uint32_t lvl = dl <= 0 ? 0u : (dl <= avail * m.delay_thr ? 1u : 2u);
-    const uint32_t state = ((fb * (uint32_t)m.K) + (uint32_t)k) * 3u + lvl;
+    const uint32_t lvl = dl <= 0 ? 0u : (dl <= avail * m.dec.delay_thr ? 1u : 2u);
+    const uint32_t state = ((fb * (uint32_t)m.dec.K) + (uint32_t)k) * 3u + lvl;
     const uint32_t w = pr[1] >> 16, roff = pr[3] + state * w;
     const bool row_ok = pos_k >= 0 && dd < DIST_INF && (pin >> 2) == sw && slot < np;
     const uint32_t qoff = pp[3] + ((pend >> 14) & 0x3FFFu) * (pp[1] >> 16) + ((pend >> 28) & 3u);
@@ -1777,7 +1805,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
         am |= ok << a;
       }
       const int mind = (int)((rd >> 16) & 15u);
-      double mx = mind != 15 ? m.default_q : -__builtin_huge_val();
+      double mx = mind != 15 ? m.dec.default_q : -__builtin_huge_val();
       int best = mind != 15 ? mind : 99, arg = -1;
       double amx = 0.0;
 #pragma unroll
@@ -1867,6 +1895,10 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
       prefetch(greedy);
       pf_ok = !PART && !EXT;  // (PART, EXT: only this decision's train is staged: the next one stages its own)
     }
+    // PHASE_BLK: the map's scalars of the decision, behind the staging (whose own reads would only push them out)
+    Blk<MapDecide> md = m.dec;
+    Blk<int32_t> ntab = m.lrn.ntab;
+    if constexpr (PHASE_BLK) __builtin_amdgcn_sched_barrier(0);
     const int h = mctz(q_mask);
     if (!observe_only) mclear_low(q_mask);
     const uint32_t sd = trl(sdec, h);
@@ -1894,7 +1926,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     // (past the table nothing is loaded: the pow path below)
     double eps_tab_v = 0.0;
     if constexpr (EPS_EARLY) {
-      if (n_sw < (uint32_t)m.ntab) eps_tab_v = ld(eps_row(), (size_t)n_sw);
+      if (n_sw < (uint32_t)ntab) eps_tab_v = ld(HPG ? eps_row() : md.eps_tab, (size_t)n_sw);
       __builtin_amdgcn_sched_barrier(0);
     }
     const Mask malf = malf_kept();
@@ -1927,8 +1959,8 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     const int32_t d_obs = observe_only ? dist(k, p0, (int)tb_dir(b)) : dist_staged(d16_lo(U(pfd01[0])));
     const int32_t dl = now - la + d_obs;
     const int32_t avail = la - ed;
-    const uint32_t lvl = dl <= 0 ? 0u : (dl <= avail * m.delay_thr ? 1u : 2u);
-    const uint32_t state = ((free_bits * (uint32_t)m.K) + (uint32_t)k) * 3u + lvl;
+    const uint32_t lvl = dl <= 0 ? 0u : (dl <= avail * md.delay_thr ? 1u : 2u);
+    const uint32_t state = ((free_bits * (uint32_t)md.K) + (uint32_t)k) * 3u + lvl;
     const uint32_t la7 = (uint32_t)lid() & 7u;
     const uint32_t srca = (swr.w[1] >> (2u * la7)) & 3u, dsta = (swr.w[1] >> (16u + 2u * la7)) & 3u;
     const uint32_t amask =
@@ -2004,9 +2036,9 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
       if (xp::kEpsConst) {
         explore = ud < eps0_();
       } else if constexpr (EPS_EARLY) {
-        explore = ud < (n < (uint32_t)m.ntab ? eps_tab_v : eps0_() * pow_ool(eps_decay_(), (double)n));
+        explore = ud < (n < (uint32_t)ntab ? eps_tab_v : eps0_() * pow_ool(eps_decay_(), (double)n));
       } else {
-        explore = ud < (n < (uint32_t)m.ntab ? LDC(eps_row(), (size_t)n) : eps0_() * pow_ool(eps_decay_(), (double)n));
+        explore = ud < (n < (uint32_t)ntab ? LDC(HPG ? eps_row() : md.eps_tab, (size_t)n) : eps0_() * pow_ool(eps_decay_(), (double)n));
       }
       if (explore && !observe_only) {
         const uint32_t sub_seed = pcg_bounded(rng, 2147483646u);
@@ -2016,8 +2048,8 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
         // draw, and a device without the table, run the sub-generator itself
         uint32_t pick = 0;
         bool slow = nvalid > 1u;
-        if (slow && m.seedseq32) {
-          const uint64_t mm = (uint64_t)(xp::kNoSeedSeqLoad ? (uint32_t)mix64(U(sub_seed)) : LDC(m.seedseq32, (size_t)U(sub_seed))) * nvalid;
+        if (slow && m.dec.seedseq32) {
+          const uint64_t mm = (uint64_t)(xp::kNoSeedSeqLoad ? (uint32_t)mix64(U(sub_seed)) : LDC(m.dec.seedseq32, (size_t)U(sub_seed))) * nvalid;
           // Lemire rejects when the low word is below (2^32 - n) % n < n: test against n first
           slow = (uint32_t)mm < nvalid && (uint32_t)mm < (0u - nvalid) % nvalid;
           pick = (uint32_t)(mm >> 32);
@@ -2082,8 +2114,8 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
       mx = __longlong_as_double(((long long)RL((uint32_t)(__double_as_longlong(v_c) >> 32), cb) << 32) |
                                 (long long)RL((uint32_t)__double_as_longlong(v_c), cb));
       best = (int)((rd >> (4 * cb)) & 15u);
-      if (mind != 15 && (m.default_q > mx || (m.default_q == mx && mind < best))) {
-        mx = m.default_q;
+      if (mind != 15 && (m.dec.default_q > mx || (m.dec.default_q == mx && mind < best))) {
+        mx = m.dec.default_q;
         best = mind;
       }
       arg = (int)((rd >> (4 * ca)) & 15u);
@@ -2240,10 +2272,14 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
       post_part(d, greedy);
       return;
     }
+    Blk<MapLearn> ml = m.lrn;
+    Blk<MapUpdate> mu = m.upd;
+    Blk<StateLearn> sl = s.lrn;
+    if constexpr (PHASE_BLK) __builtin_amdgcn_sched_barrier(0);
     if (BANK || greedy) {
       if (lid() == 0) {
-        if (d.touch_cur) touch_row(d.row_cur);
-        st(sbase(), slot_ix(d.next_sw, d.h), slot_make(PEND_NONE, d.r_new, epoch));
+        if (d.touch_cur) touch_row(ml, sl, d.row_cur);
+        st(sbase(ml, sl), slot_ix(ml, d.next_sw, d.h), slot_make(PEND_NONE, d.r_new, epoch));
       }
       return;
     }
@@ -2256,11 +2292,13 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
       ps = (int)(pend & 0xFFFu);
       // ROW_PEND_POST: the pending update's key-set row from the port record in LDS, as decide() computed it
       if constexpr (ROW_PEND_POST) row_pend = port_rec(4 * ps + (int)((pend >> 12) & 3u)).row_base() + ((pend >> 14) & 0x3FFFu);
-      const double lr = lr_of(cget(ps));
+      double lr;
+      if constexpr (PHASE_BLK) lr = lr_of(ml, mu, [&] { return cget(ps); });
+      else lr = lr_of(cget(ps));
       const double r = (double)d.reward;
       if (d.sw != ps) {
         const double a1 = (1.0 - lr) * d.q_pend;
-        const double b1 = lr * (r + m.gamma * d.mq);
+        const double b1 = lr * (r + mu.gamma * d.mq);
         nv = a1 + b1;
       } else {
         const double a1 = (1.0 - lr) * d.q_pend;
@@ -2275,13 +2313,13 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
         if (rep == 1 && !(xp::kQStoreTwice || xp::kTouchTwice || xp::kSlotTwice)) break;
         if (rep == 1) asm volatile("" ::: "memory");
         if (hp) {
-          if (!xp::kNoQStore && (rep == 0 || xp::kQStoreTwice)) st(qbase(), (size_t)d.qoff_pend, nv);
-          if (!xp::kNoTouch && (rep == 0 || xp::kTouchTwice)) touch_row(row_pend);
+          if (!xp::kNoQStore && (rep == 0 || xp::kQStoreTwice)) st(qbase(ml, sl), (size_t)d.qoff_pend, nv);
+          if (!xp::kNoTouch && (rep == 0 || xp::kTouchTwice)) touch_row(ml, sl, row_pend);
         }
-        if (!xp::kNoTouch && (rep == 0 || xp::kTouchTwice) && (d.touch_cur || (hp && d.sw != ps))) touch_row(d.row_cur);
+        if (!xp::kNoTouch && (rep == 0 || xp::kTouchTwice) && (d.touch_cur || (hp && d.sw != ps))) touch_row(ml, sl, d.row_cur);
         if (!xp::kNoSlot && (rep == 0 || xp::kSlotTwice)) {
-          st(sbase(), slot_ix(d.sw, d.h), slot_make(PEND_NONE, slot_rew(d.slotword, epoch), epoch));
-          st(sbase(), slot_ix(d.next_sw, d.h),
+          st(sbase(ml, sl), slot_ix(ml, d.sw, d.h), slot_make(PEND_NONE, slot_rew(d.slotword, epoch), epoch));
+          st(sbase(ml, sl), slot_ix(ml, d.next_sw, d.h),
              slot_make(pend_make((uint32_t)d.sw, (uint32_t)d.slot, d.state, (uint32_t)d.j), d.r_new, epoch));
         }
       }
@@ -2296,9 +2334,9 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     while (many(fresh)) {
       const int tr = mctz(fresh);
       mclear_low(fresh);
-      for (int base = 0; base < m.S; base += G) {
+      for (int base = 0; base < m.lrn.S; base += G) {
         const int sw2 = base + lid();
-        const bool valid = sw2 < m.S;
+        const bool valid = sw2 < m.lrn.S;
         const uint64_t slw = valid ? ld(sbase(), slot_ix(sw2, tr)) : 0ull;
         const uint32_t pe = valid ? slot_pend(slw, epoch) : PEND_NONE;
         const int ps = pe == PEND_NONE ? 0 : (int)(pe & 0xFFFu);
@@ -2311,7 +2349,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
         const u4 pr = port_v(4 * ps + pslot);
         double* qp = qbase() + pr[3] + (size_t)pstate * (pr[1] >> 16) + pj;
         const double a1 = (1.0 - lr) * ld(qp, 0);
-        const double b1 = lr * (1000.0 + m.gamma * 0.0);
+        const double b1 = lr * (1000.0 + m.upd.gamma * 0.0);
         st(qp, 0, a1 + b1);
         touch_row(pr[2] + pstate);
         st(sbase(), slot_ix(sw2, tr), slot_make(PEND_NONE, slot_rew(slw, epoch), epoch));
@@ -2339,7 +2377,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     const bool loc_p = local_sw(ps);
     const double lr = lr_of(cget(ps));
     const double r = (double)d.reward;
-    const double target = d.sw != ps ? r + m.gamma * d.mq : r;
+    const double target = d.sw != ps ? r + m.upd.gamma * d.mq : r;
     // record slots taken outside the lane-0 region, so the count stays wave-uniform
     const bool upd_rec = hp && !loc_p;
     const bool touch_rec = hp && d.sw != ps && !d.touch_cur && !loc_cur;
@@ -2376,9 +2414,9 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
       const int tr = mctz(fresh);
       mclear_low(fresh);
       const uint32_t n_before = n_upd;
-      for (int base = 0; base < m.S; base += G) {
+      for (int base = 0; base < m.lrn.S; base += G) {
         const int sw2 = base + lid();
-        const bool valid = sw2 < m.S;
+        const bool valid = sw2 < m.lrn.S;
         const uint64_t slw = valid ? ld(sbase(), slot_ix(sw2, tr)) : 0ull;
         const uint32_t pe = valid ? slot_pend(slw, epoch) : PEND_NONE;
         const int ps2 = pe == PEND_NONE ? 0 : (int)(pe & 0xFFFu);
@@ -2398,11 +2436,11 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
           double* qp = qbase() + (uint32_t)ld(P->q_off_own, (size_t)g) + (size_t)pstate * (pr[1] >> 16) + pj;
           const double lr2 = lr_of_var(n);
           const double a1 = (1.0 - lr2) * ld(qp, 0);
-          const double b1 = lr2 * (1000.0 + m.gamma * 0.0);
+          const double b1 = lr2 * (1000.0 + m.upd.gamma * 0.0);
           st(qp, 0, a1 + b1);
           touch_row(ld(P->row_own, (size_t)g) + pstate);
         } else {
-          emit_upd(k, ps2, pslot, pstate, pj, 0u, lr_of_var(n), 1000.0 + m.gamma * 0.0, (int)stage);
+          emit_upd(k, ps2, pslot, pstate, pj, 0u, lr_of_var(n), 1000.0 + m.upd.gamma * 0.0, (int)stage);
         }
         st(sbase(), slot_ix(sw2, tr), slot_make(PEND_NONE, slot_rew(slw, epoch), epoch));
       }
@@ -2834,7 +2872,7 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
   // (LM shapes are launched two blocks to a CU: both blocks' LDS must fit its 160 KB)
   static_assert(!LM || 2 * (O_LM + LM_WORDS) * 4 <= 163840, "LM: two blocks' LDS exceed a CU's 160 KB");
   __shared__ __attribute__((aligned(16))) uint32_t lds[O_LM + LM_WORDS];
-  for (int i = (int)threadIdx.x; i < m.S * V::SW_LDS; i += (int)blockDim.x)
+  for (int i = (int)threadIdx.x; i < m.lrn.S * V::SW_LDS; i += (int)blockDim.x)
     lds[O_SW + i] = m.sw_pack[(i / V::SW_LDS) * 16 + i % V::SW_LDS];
   for (int i = (int)threadIdx.x; i < m.NP * 4; i += (int)blockDim.x) {
     lds[O_PP + i] = m.port_pack[i];
@@ -2842,7 +2880,7 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
   }
   const int lm_mv = LM ? m.HW * 16 : 0;  // move-table words
   if constexpr (LM) {
-    const int nd = m.K * m.HW * 4;  // distance entries
+    const int nd = m.dec.K * m.HW * 4;  // distance entries
     for (int i = (int)threadIdx.x; i < lm_mv; i += (int)blockDim.x) lds[O_LM + i] = m.move_tab[i];
     for (int j = (int)threadIdx.x; 2 * j < nd; j += (int)blockDim.x) {
       const uint32_t lo = d16(m.dist[2 * j]), hi = 2 * j + 1 < nd ? d16(m.dist[2 * j + 1]) : 0u;

@@ -13,8 +13,20 @@ into the phase's function (tick(), prefetch_slot(), ...), so the chains of a blo
   staging      exposed round trips    4   loads   14   per wait  3.50
       wait @1766  <- 5 loads @1739 1777 1739 1739 1739
 
+`--counter lgkm` counts the other counter the same way: the operations are the LDS instructions (`ds_*`, reads, writes
+and `ds_bpermute` alike -- all of them count on lgkmcnt) and the scalar loads (`s_load*`, `s_buffer_load*`), the waits
+every `s_waitcnt` with an `lgkmcnt(N)` operand; a wait with `vmcnt` alone retires none of them.  A wait is listed under
+each kind it retires an operation of, with the waits that retire a single operation of the kind counted apart (those
+are the serial ones: a field loaded where it is used, a record read behind the value that indexes it), and `--lines`
+marks every operation `s:` (scalar load) or `d:` (LDS):
+
+  post         exposed waits   30   ops   52   per wait  1.73   scalar   25 (single  23)   LDS    5 (single   5)
+      wait @2263  <- 1 op @s:2263
+
 Usage: python scripts/load_chains.py [--tu sfl_kwave_v7.hip] [--kernel SUBSTR] [--csrc DIR] [--listing FILE.s] [--lines]
+                                     [--counter vm|lgkm]
   --lines    list every exposed wait with its loads (default: the per-phase table only)
+  --counter  vm (default): vector-memory loads against vmcnt; lgkm: LDS instructions and scalar loads against lgkmcnt
 """
 import argparse
 import os
@@ -26,7 +38,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import phase_listing as pl  # noqa: E402
 
 LOADS = ("global_load", "flat_load")
+SCALAR_LOADS = ("s_load", "s_buffer_load")
 WAIT = "s_waitcnt"
+KINDS = (("s", "scalar"), ("d", "LDS"))
 # calls of sfl_wave.h that only pass on to the function doing the work: the source line reported is the callee's
 PASS_THROUGH = r"\bprefetch_slot\("
 
@@ -37,6 +51,19 @@ def is_load(op):
 
 def is_vm_wait(op, args):
     return op == WAIT and "vmcnt(" in args
+
+
+def lgkm_kind(op):
+    """'d' for an LDS instruction, 's' for a scalar load, None for anything else."""
+    if op.startswith("ds_"):
+        return "d"
+    if op.startswith(SCALAR_LOADS):
+        return "s"
+    return None
+
+
+def is_lgkm_wait(op, args):
+    return op == WAIT and "lgkmcnt(" in args
 
 
 def pass_lines(wave_h):
@@ -65,8 +92,10 @@ def place(cur, sites, passthru):
     return phase, where
 
 
-def chains(lines, sites=None, passthru=(), kernel=""):
-    """{kernel: [(phase, wait line, [load lines])]}: the exposed waits of each kernel in listing order."""
+def chains(lines, sites=None, passthru=(), kernel="", counter="vm"):
+    """{kernel: [(phase, wait line, [load lines])]}: the exposed waits of each kernel in listing order.
+    counter "lgkm": the LDS instructions and scalar loads against lgkmcnt, each as (kind, line)."""
+    lgkm = counter == "lgkm"
     sites = sites or {}
     res, name, cur, pending = {}, None, None, []
     for line in lines:
@@ -90,9 +119,11 @@ def chains(lines, sites=None, passthru=(), kernel=""):
             continue
         parts = s.split(";")[0].split(None, 1)
         op, args = parts[0], parts[1] if len(parts) > 1 else ""
-        if is_load(op):
+        if lgkm and lgkm_kind(op):
+            pending.append((lgkm_kind(op), place(cur, sites, passthru)[1]))
+        elif not lgkm and is_load(op):
             pending.append(place(cur, sites, passthru)[1])
-        elif is_vm_wait(op, args) and pending:
+        elif (is_lgkm_wait(op, args) if lgkm else is_vm_wait(op, args)) and pending:
             phase, where = place(cur, sites, passthru)
             res[name].append((phase, where, pending))
             pending = []
@@ -108,6 +139,41 @@ def summary(waits):
     return out
 
 
+def kind_split(waits):
+    """{phase: {kind: (waits that retire an operation of the kind, of them retiring just one of the kind)}} (lgkm)"""
+    out = {}
+    for phase, _, ops in waits:
+        for k in sorted({k for k, _ in ops}):
+            n, one = out.setdefault(phase, {}).get(k, (0, 0))
+            out[phase][k] = (n + 1, one + (sum(kk == k for kk, _ in ops) == 1))
+    return out
+
+
+def print_lgkm(tu, tick_def, res, lines):
+    print(f"# {tu}: exposed LDS / scalar-load waits (lgkmcnt) per loop phase (static; source lines of sfl_wave.h, tick() at {tick_def})")
+    fmt = lambda ops: " ".join(f"{k}:{'?' if w is None else w}" for k, w in ops)  # noqa: E731
+    for name, waits in res.items():
+        print(f"\n{name}")
+        sm, ks = summary(waits), kind_split(waits)
+        tot, tot_k = [0, 0], {k: [0, 0] for k, _ in KINDS}
+        row = lambda label, n, k, kk: (  # noqa: E731
+            f"  {label:12s} exposed waits {n:4d}   ops {k:4d}   per wait {k / n if n else 0.0:5.2f}"
+            + "".join(f"   {kn} {kk[kd][0]:4d} (single {kk[kd][1]:3d})" for kd, kn in KINDS))
+        for p in pl.PHASES:
+            n, k = sm.get(p, (0, 0))
+            kk = {kd: ks.get(p, {}).get(kd, (0, 0)) for kd, _ in KINDS}
+            tot[0], tot[1] = tot[0] + n, tot[1] + k
+            for kd, _ in KINDS:
+                tot_k[kd][0] += kk[kd][0]
+                tot_k[kd][1] += kk[kd][1]
+            print(row(p, n, k, kk))
+            if lines:
+                for ph, where, ops in waits:
+                    if ph == p:
+                        print(f"      wait @{'?' if where is None else where}  <- {len(ops)} op{'s' if len(ops) != 1 else ''} @{fmt(ops)}")
+        print(row("total", tot[0], tot[1], tot_k))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--tu", default="sfl_kwave_v7.hip", choices=sorted(pl.build.TUS))
@@ -115,6 +181,7 @@ def main():
     ap.add_argument("--csrc", default=pl.build.CSRC)
     ap.add_argument("--listing")
     ap.add_argument("--lines", action="store_true")
+    ap.add_argument("--counter", default="vm", choices=("vm", "lgkm"))
     a = ap.parse_args()
     csrc = os.path.abspath(a.csrc)
     wave_h = os.path.join(csrc, "sfl_wave.h")
@@ -124,7 +191,7 @@ def main():
         if not listing:
             listing = os.path.join(tmp, os.path.splitext(a.tu)[0] + ".s")
             pl.compile_listing(a.tu, csrc, listing)
-        res = chains(open(listing), sites, pass_lines(wave_h), a.kernel)
+        res = chains(open(listing), sites, pass_lines(wave_h), a.kernel, a.counter)
     if not res:
         raise SystemExit("no kernel matched")
     # (a listing read against another tree's sfl_wave.h, or one built without -gline-tables-only, attributes next to
@@ -133,6 +200,8 @@ def main():
     if wave and 10 * sum(ph != "loop" for ph in wave) < len(wave):
         raise SystemExit("fewer than a tenth of the wave kernels' waits could be attributed to a loop phase -- "
                          "does --csrc match the listing?")
+    if a.counter == "lgkm":
+        return print_lgkm(a.tu, tick_def, res, a.lines)
     print(f"# {a.tu}: exposed vector-memory round trips per loop phase (static; source lines of sfl_wave.h, tick() at {tick_def})")
     fmt = lambda xs: " ".join("?" if x is None else str(x) for x in xs)  # noqa: E731
     for name, waits in res.items():
