@@ -9,7 +9,10 @@ scores each experiment's table on N seeded greedy episodes in one device batch (
 same scenario (equal [ENV] sections, and equal random_seed where the map is generated from it) share a batch as its
 policies, env i runs seed S + i (default S: the config's random_seed, so env 0 is the episode the plain evaluation
 runs), results go to EXP_DIR/eval_batch/summary.json and per_env.npz; with --diagnose [--stall S] every train that did
-not arrive is classified on the device as well (eval_batch/nonarrivals.json).
+not arrive is classified on the device as well (eval_batch/nonarrivals.json); with --record K up to K episodes per
+experiment are recorded on the device in a second, identical evaluation -- with --diagnose the first K whose env has a
+stalled train (classes 4 - 6), otherwise the first K -- and written as eval_batch/episode_<seed>.npz
+(runtime.Episode) beside eval_batch/traffic.npz, and with --frames rendered into eval_batch/frames_<seed>/iter_<n>.png.
 """
 import argparse
 import configparser
@@ -65,7 +68,8 @@ def _scenario_key(config):
     return tuple(sorted(env.items())), None if from_file else int(config["MISC"]["random_seed"])
 
 
-def evaluate_batch(exp_dirs, n_envs, model_file="distr_q_model.pkl", seed0=None, lib=None, diagnose=False, stall=30):
+def evaluate_batch(exp_dirs, n_envs, model_file="distr_q_model.pkl", seed0=None, lib=None, diagnose=False, stall=30,
+                   record=0, frames=False):
     """Each experiment's saved Q-table on ``n_envs`` greedy episodes, env i on seed ``seed0 + i`` (default ``seed0``:
     the experiment's ``random_seed``), in one device batch per group of experiments on the same scenario: the group's
     tables are the policies of one ``runtime.EvalBatch`` of ``len(group) * n_envs`` envs.  Experiments share a scenario
@@ -77,7 +81,12 @@ def evaluate_batch(exp_dirs, n_envs, model_file="distr_q_model.pkl", seed0=None,
     [n_envs][T], ``trains_at_dest`` as ``evaluate`` saves it for env 0).  Returns {exp_dir: summary}.
     With ``diagnose`` every train that did not arrive is classified on the device (``EvalBatch.diagnose`` with the window
     ``stall``) and ``EXP_DIR/eval_batch/nonarrivals.json`` holds the policy's class counts, their per-episode means and
-    the ten cells with the most stalled trains as (row, column, count); the other files are what they are without it."""
+    the ten cells with the most stalled trains as (row, column, count); the other files are what they are without it.
+    With ``record`` = K > 0 a second, identical evaluation records up to K envs per experiment on the device
+    (``EvalBatch.record``): with ``diagnose`` the first K envs that have a train of class 4 - 6, otherwise the first K.
+    ``EXP_DIR/eval_batch/episode_<seed>.npz`` holds each (``runtime.Episode.load``), ``traffic.npz`` the experiment's
+    recorded traffic (``EvalBatch.traffic``) and the recorded seeds; ``frames`` also renders every recorded decision
+    into ``EXP_DIR/eval_batch/frames_<seed>/iter_<n>.png``.  Without ``record`` every file is what it is today."""
     runtime = importlib.import_module(PKG + ".runtime")
     n_envs = int(n_envs)
     if n_envs < 1:
@@ -114,6 +123,21 @@ def evaluate_batch(exp_dirs, n_envs, model_file="distr_q_model.pkl", seed0=None,
             if diagnose:
                 dg = ev.diagnose(stall, per_env=False)["table"]
                 hot = [ev.hotspots(p) for p in range(P)]
+            chosen, episodes, traffic = [], [], []
+            if record > 0:
+                cls = ev.diagnose(stall)["cls"] if diagnose else None
+                for p in range(P):
+                    envs = list(range(p * n_envs, (p + 1) * n_envs))
+                    if diagnose:
+                        envs = [e for e in envs if (cls[:, e] >= 4).any()]
+                    chosen.append(envs[:int(record)])
+                flat = [e for es in chosen for e in es]
+                if flat:
+                    ev.record(flat)
+                    again = ev.evaluate([p for p in range(P) for _ in range(n_envs)])
+                    assert np.array_equal(again["cum_reward"], out["cum_reward"]), "the second evaluation differs"
+                    episodes = [ev.recording(k) for k in range(len(flat))]
+                    traffic = [ev.traffic(p) for p in range(P)]
         finally:
             ev.close()
         for p, (exp_dir, _) in enumerate(members):
@@ -142,6 +166,19 @@ def evaluate_batch(exp_dirs, n_envs, model_file="distr_q_model.pkl", seed0=None,
                            hot_cells=[[i // W, i % W, int(hot[p].ravel()[i])] for i in top])
                 with open(os.path.join(out_dir, "nonarrivals.json"), "w") as f:
                     json.dump(rec, f, indent=1)
+            if record > 0:
+                mine = [ep for ep in episodes if ep.policy == p and ep.env in chosen[p]]
+                for ep in mine:
+                    ep.save(os.path.join(out_dir, f"episode_{ep.seed}.npz"))
+                    if frames:
+                        render = importlib.import_module(PKG + ".render")
+                        fdir = os.path.join(out_dir, f"frames_{ep.seed}")
+                        os.makedirs(fdir, exist_ok=True)
+                        for n, img in enumerate(render.frames_at_decisions(env.compiled, ep)):
+                            render.save_png(os.path.join(fdir, f"iter_{n}.png"), img)
+                tr = traffic[p] if traffic else {}
+                np.savez_compressed(os.path.join(out_dir, "traffic.npz"), seeds=np.array([ep.seed for ep in mine], np.int64),
+                                    envs=np.array([ep.env - p * n_envs for ep in mine], np.int64), **tr)
     return results
 
 
@@ -155,8 +192,14 @@ if __name__ == "__main__":
     ap.add_argument("--diagnose", action="store_true",
                     help="with --batch: classify every non-arrival on the device (eval_batch/nonarrivals.json)")
     ap.add_argument("--stall", type=int, default=30, help="with --diagnose: ticks without a move that make a train stalled")
+    ap.add_argument("--record", type=int, default=0, metavar="K",
+                    help="with --batch: record up to K episodes per experiment on the device (eval_batch/episode_<seed>.npz, "
+                         "traffic.npz); with --diagnose those of envs with a stalled train")
+    ap.add_argument("--frames", action="store_true",
+                    help="with --record: render every recorded decision (eval_batch/frames_<seed>/iter_<n>.png)")
     args = ap.parse_args()
     if args.batch > 0:
-        evaluate_batch(args.exp_dirs, args.batch, args.model, args.seed0, diagnose=args.diagnose, stall=args.stall)
+        evaluate_batch(args.exp_dirs, args.batch, args.model, args.seed0, diagnose=args.diagnose, stall=args.stall,
+                       record=args.record, frames=args.frames)
     else:
         evaluate(args.exp_dirs, args.model)

@@ -47,6 +47,10 @@
  *   sfl_create_eval / sfl_bank_eval   DistrQLearning.load + test (distr_q.py:510-527, 184-241) as eval.py runs them
  *                     (eval.py:85-97), for a bank of tables shared by many seeded envs: one greedy episode per env,
  *                     the per-table arrival statistics reduced on the device
+ *   sfl_bank_record / sfl_bank_record_read   DistrQLearning.test(plot=True) and ASyncSwitchEnv.render
+ *                     (distr_q.py:216-221): the listed envs' bank episodes recorded on the device, every train after
+ *                     every tick and every decision, to be rendered on the host; sfl_bank_record_traffic reduces
+ *                     them to per-cell and per-switch traffic counts on the device
  *   sfl_get_phase_cycles  the per-phase time accumulators            switchfl/switch_env.py:67-73
  *                     (flatland_step_time, last_time, action_selection_time, update_time, reset_time ...)
  */
@@ -673,6 +677,78 @@ int sfl_bank_diag(sfl_handle* h, int32_t stall, sfl_diag_out* out /* may be NULL
 int sfl_bank_diag_read(sfl_handle* h, sfl_diag_cell* out /* [n_policies] */);
 int sfl_bank_diag_hot(sfl_handle* h, uint32_t p, uint32_t* out /* [H*W] */);
 int sfl_bank_diag_ms(sfl_handle* h, double* last_ms, double* total_ms /* either may be NULL */);
+
+/* ---- policy-bank evaluation: episodes recorded on the device ----
+ * sfl_bank_diag names the class of a train that did not arrive; a recording shows the episode that led there: every
+ * train after every tick, and every decision.  sfl_bank_eval starts every env from a reset and replays the same
+ * episode, so a second evaluation with the jammed envs recorded shows exactly the episodes the diagnosis classified.
+ * THE RULE -- the host build and the kernels implement it exactly; every word is an integer, nothing has a tolerance.
+ * sfl_bank_record(h, n, envs, tick_cap, dec_cap) arms a recording of the n listed envs (distinct, any order; slot k is
+ * envs[k]) on an evaluation handle; an armed recording is replaced, n == 0 disarms and frees it.  Every later
+ * sfl_bank_eval then records, for slot k, from the one greedy episode of env e = envs[k]:
+ *   frames     after each Flatland tick t = 1 .. min(ticks, tick_cap) of the episode, for every train h:
+ *                cell[k][t-1][h]   int32: the train's cell r * W + c after the tick, -1 off the map;
+ *                bits[k][t-1][h]   uint32: the train's state word after the tick -- heading in bits 0-1, train state in
+ *                                  bits 2-4 (0 WAITING, 1 READY_TO_DEPART, 2 MALFUNCTION_OFF_MAP, 3 MOVING, 4 STOPPED,
+ *                                  5 MALFUNCTION, 6 DONE), malfunction counter in bits 13-20, every other bit 0.
+ *              The first tick_cap ticks are kept, later ones dropped.
+ *   decisions  one row of SFL_REC_DEC_WORDS int32 per decision d = 0 .. min(decisions, dec_cap) - 1, in the order
+ *              SFL_REC_NOW .. SFL_REC_STEP_NOW: now, switch, train, slot, state, mask, action, reward, next_switch,
+ *              step_now, with the meanings of the same-named sfl_env_io fields (switch: its `agent`): now is
+ *              _elapsed_steps when the decision was observed, step_now when its step() returned (the ticks that follow
+ *              the last decision of a batch lie between the two).  A truncated episode has max_steps + 1 decisions.
+ *   counts     the episode's true ticks and decisions (sfl_eval_out.ticks / .decisions of env e): a slot is complete when
+ *              ticks <= tick_cap and decisions <= dec_cap.  Words past the kept frames and rows mean nothing.
+ * The buffers belong to the handle: n * (tick_cap * T * 8 + dec_cap * 4 * SFL_REC_DEC_WORDS) bytes, at most
+ *   SFL_REC_MAX_BYTES.  A recording changes no output of sfl_bank_eval or sfl_bank_diag* and no env's end state; with
+ *   none armed an evaluation on the wave kernels launches kernels that hold none of the recording's code (the recording
+ *   kernels are instantiations of their own, launched only while one is armed), and the lane-per-env body and the host
+ *   build test one null pointer per tick and decision; nothing more is written either way.
+ * Readers, synchronous on the handle's stream: sfl_bank_record_info (n, the caps, the row's word count; n = 0: none
+ *   armed); sfl_bank_record_counts ([n] ticks, [n] decisions); sfl_bank_record_read (slot k's arrays, [tick_cap][T],
+ *   [tick_cap][T], [dec_cap][SFL_REC_DEC_WORDS]; a NULL pointer skips one).
+ * sfl_bank_record_traffic(h, p, out) reduces, on the device, the kept frames and rows of the slots whose env followed
+ *   policy p in the last evaluation -- the while-it-happens companion of sfl_bank_diag_hot, which sees final cells only:
+ *     occupancy[H*W]              train-ticks on each cell (kept frames with cell >= 0);
+ *     standing[H*W]               those whose train held the same cell one tick earlier (frame t-1 against t-2; the
+ *                                 frame of tick 1 never counts: every train is off the map before it);
+ *     standing_malfunction[H*W]   the part of standing where the train's state after the tick is MALFUNCTION;
+ *     decisions[S]                kept rows per switch;     stops[S]   those whose action is the switch's STOP (its last).
+ *   All integer sums: the order of the fold does not matter.  Every pointer of sfl_record_traffic is an optional host
+ *   array.  sfl_bank_record_ms: the device time of the last traffic fold and of all since create (0 on the host build).
+ * Refused, with a message in sfl_last_error and the handle usable: a handle that is no evaluation handle; an env >=
+ *   n_envs or listed twice; a cap < 1; a size over SFL_REC_MAX_BYTES; a reader (counts, read, traffic) with no recording
+ *   armed or before a successful sfl_bank_eval that followed the arming; k >= n; p >= n_policies. */
+#define SFL_REC_DEC_WORDS    10
+#define SFL_REC_MAX_BYTES    (1ull << 30)
+#define SFL_REC_NOW          0
+#define SFL_REC_SWITCH       1
+#define SFL_REC_TRAIN        2
+#define SFL_REC_SLOT         3
+#define SFL_REC_STATE        4
+#define SFL_REC_MASK         5
+#define SFL_REC_ACTION       6
+#define SFL_REC_REWARD       7
+#define SFL_REC_NEXT_SWITCH  8
+#define SFL_REC_STEP_NOW     9
+typedef struct {            /* what sfl_bank_record_info reports */
+  uint32_t n;               /* recorded envs (0: no recording armed) */
+  int32_t tick_cap, dec_cap;
+  uint32_t dec_words;       /* SFL_REC_DEC_WORDS */
+} sfl_record_info;
+typedef struct {            /* optional host outputs of sfl_bank_record_traffic */
+  uint32_t* occupancy;             /* [H*W] */
+  uint32_t* standing;              /* [H*W] */
+  uint32_t* standing_malfunction;  /* [H*W] */
+  uint32_t* decisions;             /* [S] */
+  uint32_t* stops;                 /* [S] */
+} sfl_record_traffic;
+int sfl_bank_record(sfl_handle* h, uint32_t n, const uint32_t* envs /* [n] */, int32_t tick_cap, int32_t dec_cap);
+int sfl_bank_record_info(sfl_handle* h, sfl_record_info* out);
+int sfl_bank_record_counts(sfl_handle* h, int32_t* ticks /* [n] */, int32_t* decisions /* [n]; either may be NULL */);
+int sfl_bank_record_read(sfl_handle* h, uint32_t k, int32_t* cell, uint32_t* bits, int32_t* dec /* any may be NULL */);
+int sfl_bank_record_traffic(sfl_handle* h, uint32_t p, sfl_record_traffic* out);
+int sfl_bank_record_ms(sfl_handle* h, double* last_ms, double* total_ms /* either may be NULL */);
 
 /* ---- suspend and resume: a batch's state and its live Q rows, packed on the device ----
  * Everything a launch leaves behind is the per-env state, the key set and the Q block of each env.  A capture of n

@@ -71,6 +71,12 @@ EVAL_FIELDS = ("episodes", "trains_early", "trains_late", "trains_not_arrived", 
 DIAG_FIELDS = ("episodes", "truncated", "never_departed", "moving_late", "stop_loop", "deadlock_queue", "deadlock_cycle",
                "cycles", "episodes_jammed", "stalled_in_malfunction", "stalled_for_sum", "stalled_for_max")
 DIAG_CLASSES = ("arrived", "truncated", "never_departed", "moving_late", "stop_loop", "deadlock_queue", "deadlock_cycle")
+# include/sfl.h SFL_REC_*: the words of a recorded decision's row in order, the size limit of a recording, and the fields
+# of sfl_record_traffic
+REC_DEC_FIELDS = ("now", "switch", "train", "slot", "state", "mask", "action", "reward", "next_switch", "step_now")
+REC_MAX_BYTES = 1 << 30
+TRAFFIC_FIELDS = ("occupancy", "standing", "standing_malfunction", "decisions", "stops")
+TRAIN_STATES = ("WAITING", "READY_TO_DEPART", "MALFUNCTION_OFF_MAP", "MOVING", "STOPPED", "MALFUNCTION", "DONE")
 BANK_FROM_ENV = 0
 BANK_FROM_COHORT = 1
 CURVE_MAX_TABLE_BYTES = 64 << 20
@@ -111,6 +117,17 @@ class EvalOut(C.Structure):
 class DiagOut(C.Structure):
     """sfl_diag_out: the optional per-train outputs of sfl_bank_diag."""
     _fields_ = [("cls", P(C.c_uint8)), ("blocker", P(C.c_int16)), ("stalled_for", P(C.c_int32))]
+
+
+class RecordInfo(C.Structure):
+    """sfl_record_info: what sfl_bank_record_info reports of the armed recording."""
+    _fields_ = [("n", C.c_uint32), ("tick_cap", C.c_int32), ("dec_cap", C.c_int32), ("dec_words", C.c_uint32)]
+
+
+class RecordTraffic(C.Structure):
+    """sfl_record_traffic: the optional outputs of sfl_bank_record_traffic."""
+    _fields_ = [("occupancy", P(C.c_uint32)), ("standing", P(C.c_uint32)), ("standing_malfunction", P(C.c_uint32)),
+                ("decisions", P(C.c_uint32)), ("stops", P(C.c_uint32))]
 
 
 class StateDesc(C.Structure):
@@ -217,6 +234,12 @@ EXPORTS = {
     "sfl_bank_diag_read": (C.c_int, [C.c_void_p, P(C.c_int64)]),
     "sfl_bank_diag_hot": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_uint32)]),
     "sfl_bank_diag_ms": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double)]),
+    "sfl_bank_record": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_uint32), C.c_int32, C.c_int32]),
+    "sfl_bank_record_info": (C.c_int, [C.c_void_p, P(RecordInfo)]),
+    "sfl_bank_record_counts": (C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_int32)]),
+    "sfl_bank_record_read": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_int32), P(C.c_uint32), P(C.c_int32)]),
+    "sfl_bank_record_traffic": (C.c_int, [C.c_void_p, C.c_uint32, P(RecordTraffic)]),
+    "sfl_bank_record_ms": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double)]),
     # suspend and resume (runtime.Batch capture / restore / q_dicts)
     "sfl_state_info": (C.c_int, [C.c_void_p, P(StateDesc)]),
     "sfl_state_capture": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_uint32), P(C.c_uint64), P(C.c_uint64)]),

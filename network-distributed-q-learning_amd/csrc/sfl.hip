@@ -738,7 +738,7 @@ struct HipBackend {
     const bool bank = c.mode == sfl::MODE_BANK;
     if (variant >= 1 && variant < sfl::kNumVariants)
       sflk::launch({variant,
-                    bank ? sflk::Mode::Bank : hpg ? sflk::Mode::Hpg : c.trace ? sflk::Mode::Trace : c.phase_cyc ? sflk::Mode::Timed : sflk::Mode::Plain,
+                    bank ? (c.rec_slot ? sflk::Mode::BankRec : sflk::Mode::Bank) : hpg ? sflk::Mode::Hpg : c.trace ? sflk::Mode::Trace : c.phase_cyc ? sflk::Mode::Timed : sflk::Mode::Plain,
                     s.E, stream, pm, ps, pc});
     else sfl::with_nw(m.T, [&](auto nw) { k_run<decltype(nw)::value><<<blocks, 256, 0, stream>>>(pm, ps, pc); });
     if (!check(hipGetLastError(), "k_run launch")) return -1;
@@ -829,6 +829,14 @@ struct HipBackend {
   int diag(const sfl::DiagArgs& a) {
     check(hipEventRecord(ev0, stream), "event");
     if (sfl::LaunchErr le = sfl::diag_launch(a, (void*)stream)) return fail(le);
+    check(hipEventRecord(ev1, stream), "event");
+    return err.empty() ? 0 : -1;
+  }
+  // sfl_bank_record_traffic: the kernels of sfl_rec.hip queued on the handle's stream between the two events
+  // (elapsed_ms() after the caller's sync is their time)
+  int rec_traffic(const sfl::RecArgs& a) {
+    check(hipEventRecord(ev0, stream), "event");
+    if (sfl::LaunchErr le = sfl::rec_traffic_launch(a, (void*)stream)) return fail(le);
     check(hipEventRecord(ev1, stream), "event");
     return err.empty() ? 0 : -1;
   }

@@ -451,6 +451,40 @@ int sfl_bank_diag_ms(sfl_handle* h, double* last_ms, double* total_ms) {
   return 0;
 }
 
+// ---- episodes recorded on the device (sfl_rec.h) ----
+int sfl_bank_record(sfl_handle* h, uint32_t n, const uint32_t* envs, int32_t tick_cap, int32_t dec_cap) {
+  if (!h) return sfl::fail("sfl_bank_record: null handle");
+  return sfl::bank_record(HH(h), n, envs, tick_cap, dec_cap);
+}
+
+int sfl_bank_record_info(sfl_handle* h, sfl_record_info* out) {
+  if (!h) return sfl::fail("sfl_bank_record_info: null handle");
+  return sfl::bank_record_info(HH(h), out);
+}
+
+int sfl_bank_record_counts(sfl_handle* h, int32_t* ticks, int32_t* decisions) {
+  if (!h) return sfl::fail("sfl_bank_record_counts: null handle");
+  return sfl::bank_record_counts(HH(h), ticks, decisions);
+}
+
+int sfl_bank_record_read(sfl_handle* h, uint32_t k, int32_t* cell, uint32_t* bits, int32_t* dec) {
+  if (!h) return sfl::fail("sfl_bank_record_read: null handle");
+  return sfl::bank_record_read(HH(h), k, cell, bits, dec);
+}
+
+int sfl_bank_record_traffic(sfl_handle* h, uint32_t p, sfl_record_traffic* out) {
+  if (!h) return sfl::fail("sfl_bank_record_traffic: null handle");
+  return sfl::bank_record_traffic(HH(h), p, out);
+}
+
+int sfl_bank_record_ms(sfl_handle* h, double* last_ms, double* total_ms) {
+  if (!h) return sfl::fail("sfl_bank_record_ms: null handle");
+  if (!HH(h)->bank.on) return sfl::fail("sfl_bank_record_ms: not an evaluation handle (sfl_create_eval)");
+  if (last_ms) *last_ms = HH(h)->bank.rc_last_ms;
+  if (total_ms) *total_ms = HH(h)->bank.rc_total_ms;
+  return 0;
+}
+
 // ---- suspend and resume (sfl_snap.h) ----
 int sfl_state_info(sfl_handle* h, sfl_state_desc* out) {
   if (!h) return sfl::fail("sfl_state_info: null handle");

@@ -271,8 +271,23 @@ struct SflCtl {
   // MODE_BANK: per train the tick of its last move, L of include/sfl.h's sfl_bank_diag rule: the largest tick of the
   // episode after which the train's cell (off the map counts as one) differs from the tick before, 0 if none
   int32_t* ev_last_move;     // [T][E]
+  // MODE_BANK: the armed recording (include/sfl.h sfl_bank_record), null / 0 when none is armed.
+  // rec_slot[e] is env e's slot k, or -1: not recorded.  A recorded env writes, after tick t <= rec_tick_cap, its
+  // trains' cells and masked tr_bits words into frame t - 1 of slot k, and decision d < rec_dec_cap's row into row d
+  const int32_t* rec_slot;   // [E]
+  int32_t* rec_cell;         // [n][rec_tick_cap][T]
+  uint32_t* rec_bits;        // [n][rec_tick_cap][T]
+  int32_t* rec_dec;          // [n][rec_dec_cap][REC_DEC_WORDS]
+  int32_t rec_tick_cap, rec_dec_cap;
 };
 enum : int32_t { MODE_BANK = 3 };
+// a recorded decision's row (include/sfl.h SFL_REC_DEC_WORDS, the same-named sfl_env_io fields) and what a recorded
+// frame keeps of a train's tr_bits word: heading (bits 0-1), state (2-4), malfunction counter (13-20)
+enum : int {
+  REC_NOW = 0, REC_SWITCH, REC_TRAIN, REC_SLOT, REC_STATE, REC_MASK, REC_ACTION, REC_REWARD, REC_NEXT_SWITCH, REC_STEP_NOW,
+  REC_DEC_WORDS
+};
+enum : uint32_t { REC_BITS_MASK = 0x1Fu | (0xFFu << 13) };
 
 // External-action mode (sfl_env_step): the env alone, stepped one decision per call by a policy on the
 // host -- the PettingZoo AEC protocol agent_iter / last / step(action) / observe (switch_env.py:616-675)
@@ -1205,10 +1220,12 @@ SFL_FN void decide_apply(V& v, const Obs& o, int action, Decision& d) {
   d.next_sw = next_sw;
 }
 
+// amask_out: the observation's action mask, for MODE_BANK's recording (or null)
 template <class V>
-SFL_FN void env_decide(V& v, Decision& d, bool greedy) {
+SFL_FN void env_decide(V& v, Decision& d, bool greedy, uint32_t* amask_out = nullptr) {
   Obs o;
   decide_observe(v, o, greedy);
+  if (amask_out) *amask_out = o.amask;
   int action = o.action;
   if (!o.explore) {
     v.touch(o.sw, o.slot, o.state);
@@ -1358,6 +1375,9 @@ SFL_FN void env_run(const SflMap& m, const SflState& s, const SflCtl& c, uint32_
   double cum = s.cum_reward[e];
   const bool test_mode = c.mode == 1 || c.mode == MODE_BANK;
   int32_t* const last_move = c.ev_last_move;  // (MODE_BANK only: null otherwise)
+  // MODE_BANK with a recording armed: the env's slot in it (-1: not recorded), and its decision rows
+  const int32_t rslot = c.rec_slot ? c.rec_slot[e] : -1;
+  int32_t* const rrows = rslot >= 0 ? c.rec_dec + (size_t)rslot * (size_t)c.rec_dec_cap * REC_DEC_WORDS : nullptr;
   v.masks_load();
   while (true) {
     const bool busy = wave_any(phase == PH_DECIDE || phase == PH_POST);
@@ -1390,13 +1410,34 @@ SFL_FN void env_run(const SflMap& m, const SflState& s, const SflCtl& c, uint32_
         abytes += 36ull * (uint64_t)live;
         env_tick(v, last_move);
         ticks++;
+        if (rslot >= 0 && v.now <= c.rec_tick_cap) {  // the frame of tick v.now
+          const size_t f = ((size_t)rslot * (size_t)c.rec_tick_cap + (size_t)(v.now - 1)) * (size_t)m.T;
+          for (int h = 0; h < m.T; ++h) {
+            c.rec_cell[f + h] = s.tr_pos[v.ix(h)];
+            c.rec_bits[f + h] = s.tr_bits[v.ix(h)] & REC_BITS_MASK;
+          }
+        }
         if (v.flags & F_TERM) phase = (v.flags & F_INFLIGHT) ? PH_POST : PH_END;
         else if (!queue_empty(v)) phase = (v.flags & F_INFLIGHT) ? PH_POST : PH_DECIDE;
       }
     } else if (phase == PH_DECIDE || phase == PH_POST) {
       bool post_now = phase == PH_POST;
       if (phase == PH_DECIDE) {
-        env_decide(v, d, (v.flags & F_GREEDY) != 0);
+        uint32_t amask = 0;
+        const int32_t now_obs = v.now;
+        env_decide(v, d, (v.flags & F_GREEDY) != 0, rrows ? &amask : nullptr);
+        if (rrows && s.ep_dec[e] < c.rec_dec_cap) {  // the row's first part: the observation and the applied action
+          int32_t* r = rrows + (size_t)s.ep_dec[e] * REC_DEC_WORDS;
+          r[REC_NOW] = now_obs;
+          r[REC_SWITCH] = d.sw;
+          r[REC_TRAIN] = d.h;
+          r[REC_SLOT] = d.slot;
+          r[REC_STATE] = (int32_t)d.state;
+          r[REC_MASK] = (int32_t)amask;
+          r[REC_ACTION] = d.action;
+          r[REC_REWARD] = d.reward;
+          r[REC_NEXT_SWITCH] = d.next_sw;
+        }
         abytes += 220ull + 48ull * m.sw_np[d.sw] + 8ull * m.sw_na[d.sw];
         v.flags |= F_INFLIGHT;
         if (queue_empty(v)) phase = PH_TICK;  // ticks happen between the step and the update
@@ -1405,6 +1446,7 @@ SFL_FN void env_run(const SflMap& m, const SflState& s, const SflCtl& c, uint32_
       if (post_now) {
         if (!(v.flags & F_GREEDY)) env_post(v, d);
         if (c.trace && (int32_t)e == c.trace_env) trace_decision(v, c, d);
+        if (rrows && s.ep_dec[e] < c.rec_dec_cap) rrows[(size_t)s.ep_dec[e] * REC_DEC_WORDS + REC_STEP_NOW] = v.now;
         v.flags &= ~F_INFLIGHT;
         cum += (double)d.reward;
         s.ep_dec[e] += 1;

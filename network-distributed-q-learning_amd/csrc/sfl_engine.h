@@ -21,6 +21,7 @@
 #include "sfl_eval.h"
 #include "sfl_mfgen.h"
 #include "sfl_part.h"
+#include "sfl_rec.h"
 #include "sfl_snap.h"
 #include "sfl_trans.h"
 
@@ -175,6 +176,21 @@ struct Handle {
     bool diagnosed = false;
     float dg_last_ms = 0.f;
     double dg_total_ms = 0.0;
+    // the armed recording (sfl_bank_record*; sfl_rec.h): the listed envs on the host and the device, the
+    // per-env slot index the kernels read, the frames and the decision rows, the traffic fold's output (allocated with
+    // the handle); recorded: a successful sfl_bank_eval has followed the arming
+    uint32_t rec_n = 0;
+    int32_t rec_tick_cap = 0, rec_dec_cap = 0;
+    std::vector<uint32_t> rec_env;
+    uint32_t* rec_env_d = nullptr;   // [n]
+    int32_t* rec_slot = nullptr;     // [E]
+    int32_t* rec_cell = nullptr;     // [n][tick_cap][T]
+    uint32_t* rec_bits = nullptr;    // [n][tick_cap][T]
+    int32_t* rec_rows = nullptr;     // [n][dec_cap][SFL_REC_DEC_WORDS]
+    uint32_t* rec_out = nullptr;     // [3 * H*W + 2 * S]
+    bool recorded = false;
+    float rc_last_ms = 0.f;
+    double rc_total_ms = 0.0;
   } bank;
   // suspend and resume (sfl_state_*; sfl_snap.h): the fingerprint of the map descriptor (create), each
   // row's first cell and width on the host and the device (built at the first call), the pending capture between
@@ -613,6 +629,7 @@ int create(const sfl_map_desc* md, const sfl_hparams* hp, uint32_t n_envs, const
     bk.dg_aux = h->template dalloc<int32_t>(2 * E);
     bk.dg_hot = h->template dalloc<uint32_t>((size_t)n_policies * HW);
     bk.dg_cells = h->template dalloc<int64_t>((size_t)n_policies * DG_WORDS);
+    bk.rec_out = h->template dalloc<uint32_t>(3 * (size_t)HW + 2 * (size_t)m.lrn.S);
     m.bank_q = bk.q;
     m.bank_policy = bk.policy;
   }
@@ -1107,12 +1124,21 @@ int bank_eval(Handle<B>* h, const uint32_t* env_policy, sfl_eval_out* out) {
   c.ev_at_dest = bk.at_dest;
   c.ev_trunc = bk.trunc;
   c.ev_last_move = bk.last_move;
+  if (bk.rec_n) {
+    c.rec_slot = bk.rec_slot;
+    c.rec_cell = bk.rec_cell;
+    c.rec_bits = bk.rec_bits;
+    c.rec_dec = bk.rec_rows;
+    c.rec_tick_cap = bk.rec_tick_cap;
+    c.rec_dec_cap = bk.rec_dec_cap;
+  }
   c.launch_dec = h->d_launch_dec;
   c.launch_ticks = h->d_launch_ticks;
   c.launch_bytes = h->d_launch_bytes;
   float ms = 0.f;
   bk.folded = false;
   bk.diagnosed = false;
+  bk.recorded = false;
   int rc = h->be.run(h->map, h->st, c, h->variant, &ms);
   h->last_kernel_ms = ms;
   EvalArgs a{};
@@ -1150,6 +1176,7 @@ int bank_eval(Handle<B>* h, const uint32_t* env_policy, sfl_eval_out* out) {
   bk.total_ms += bk.last_ms;
   if (int rc2 = check_errors(h)) return rc2;
   bk.folded = true;
+  bk.recorded = bk.rec_n != 0;
   return 0;
 }
 
@@ -1225,6 +1252,172 @@ int bank_diag_hot(Handle<B>* h, uint32_t p, uint32_t* out) {
   const size_t HW = (size_t)h->map.HW;
   h->be.d2h(out, h->bank.dg_hot + (size_t)p * HW, HW * 4);
   return h->be.sync() ? fail(h->be.error()) : 0;
+}
+
+// the recording of listed envs' episodes (include/sfl.h sfl_bank_record*; sfl_rec.h): arming allocates
+// the buffers and uploads the per-env slot index, the episode launch of every later sfl_bank_eval fills them, the
+// readers copy a slot back and the traffic fold reduces the slots of one policy -- all on the handle's stream
+static_assert(REC_DEC_WORDS == SFL_REC_DEC_WORDS && REC_NOW == SFL_REC_NOW && REC_SWITCH == SFL_REC_SWITCH &&
+                  REC_TRAIN == SFL_REC_TRAIN && REC_SLOT == SFL_REC_SLOT && REC_STATE == SFL_REC_STATE &&
+                  REC_MASK == SFL_REC_MASK && REC_ACTION == SFL_REC_ACTION && REC_REWARD == SFL_REC_REWARD &&
+                  REC_NEXT_SWITCH == SFL_REC_NEXT_SWITCH && REC_STEP_NOW == SFL_REC_STEP_NOW,
+              "a recorded decision's row: the kernels' word order is the header's");
+template <class B>
+void bank_record_free(Handle<B>* h) {
+  typename Handle<B>::Bank& bk = h->bank;
+  for (void* p : {(void*)bk.rec_env_d, (void*)bk.rec_slot, (void*)bk.rec_cell, (void*)bk.rec_bits, (void*)bk.rec_rows})
+    if (p) h->dfree(p);
+  bk.rec_env_d = nullptr;
+  bk.rec_slot = nullptr;
+  bk.rec_cell = nullptr;
+  bk.rec_bits = nullptr;
+  bk.rec_rows = nullptr;
+  bk.rec_n = 0;
+  bk.rec_tick_cap = bk.rec_dec_cap = 0;
+  bk.rec_env.clear();
+  bk.recorded = false;
+}
+
+template <class B>
+int bank_record(Handle<B>* h, uint32_t n, const uint32_t* envs, int32_t tick_cap, int32_t dec_cap) {
+  typename Handle<B>::Bank& bk = h->bank;
+  if (!bk.on) return fail("sfl_bank_record: not an evaluation handle (sfl_create_eval)");
+  if (n == 0) {  // disarm
+    if (h->be.sync()) return fail(std::string("sfl_bank_record: ") + h->be.error());
+    bank_record_free(h);
+    return 0;
+  }
+  if (!envs) return fail("sfl_bank_record: null envs");
+  if (tick_cap < 1) return fail("sfl_bank_record: tick_cap " + std::to_string(tick_cap) + " (at least 1)");
+  if (dec_cap < 1) return fail("sfl_bank_record: dec_cap " + std::to_string(dec_cap) + " (at least 1)");
+  const size_t E = h->E, T = h->map.T;
+  if (n > E) return fail("sfl_bank_record: " + std::to_string(n) + " envs listed of " + std::to_string(E) + " (distinct envs only)");
+  std::vector<int32_t> slot(E, -1);
+  for (uint32_t k = 0; k < n; ++k) {
+    if (envs[k] >= E) return fail("sfl_bank_record: env " + std::to_string(envs[k]) + " of " + std::to_string(E));
+    if (slot[envs[k]] >= 0) return fail("sfl_bank_record: env " + std::to_string(envs[k]) + " is listed twice");
+    slot[envs[k]] = (int32_t)k;
+  }
+  // n * (tick_cap * T * 8 + dec_cap * 4 * SFL_REC_DEC_WORDS) bytes, in 128 bits: the caps are up to 2^31 - 1
+  const unsigned __int128 per = (unsigned __int128)(uint32_t)tick_cap * T * 8u + (unsigned __int128)(uint32_t)dec_cap * 4u * SFL_REC_DEC_WORDS;
+  if (per * n > (unsigned __int128)SFL_REC_MAX_BYTES)
+    return fail("sfl_bank_record: " + std::to_string(n) + " envs x (" + std::to_string(tick_cap) + " ticks x " + std::to_string(T) +
+                " trains x 8 + " + std::to_string(dec_cap) + " decisions x " + std::to_string(4 * SFL_REC_DEC_WORDS) +
+                ") bytes exceed SFL_REC_MAX_BYTES");
+  if (h->be.sync()) return fail(std::string("sfl_bank_record: ") + h->be.error());
+  bank_record_free(h);  // (an armed recording is replaced)
+  const size_t nf = (size_t)n * (size_t)tick_cap * T, nr = (size_t)n * (size_t)dec_cap * SFL_REC_DEC_WORDS;
+  bk.rec_env_d = h->template dalloc<uint32_t>(n);
+  bk.rec_slot = h->template dalloc<int32_t>(E);
+  bk.rec_cell = h->template dalloc<int32_t>(nf);
+  bk.rec_bits = h->template dalloc<uint32_t>(nf);
+  bk.rec_rows = h->template dalloc<int32_t>(nr);
+  if (!bk.rec_env_d || !bk.rec_slot || !bk.rec_cell || !bk.rec_bits || !bk.rec_rows) {
+    bank_record_free(h);
+    return fail("sfl_bank_record: device allocation failed");
+  }
+  h->be.h2d(bk.rec_env_d, envs, (size_t)n * 4);
+  h->be.h2d(bk.rec_slot, slot.data(), E * 4);
+  h->be.memset(bk.rec_cell, 0xFF, nf * 4);  // (words past the kept frames / rows: off the map, -1)
+  h->be.memset(bk.rec_bits, 0, nf * 4);
+  h->be.memset(bk.rec_rows, 0xFF, nr * 4);
+  if (h->be.sync()) {  // (synchronises: envs and slot are host memory)
+    bank_record_free(h);
+    return fail(std::string("sfl_bank_record: ") + h->be.error());
+  }
+  bk.rec_n = n;
+  bk.rec_tick_cap = tick_cap;
+  bk.rec_dec_cap = dec_cap;
+  bk.rec_env.assign(envs, envs + n);
+  return 0;
+}
+
+template <class B>
+int bank_record_info(Handle<B>* h, sfl_record_info* out) {
+  if (!h->bank.on) return fail("sfl_bank_record_info: not an evaluation handle (sfl_create_eval)");
+  if (!out) return fail("sfl_bank_record_info: null argument");
+  out->n = h->bank.rec_n;
+  out->tick_cap = h->bank.rec_tick_cap;
+  out->dec_cap = h->bank.rec_dec_cap;
+  out->dec_words = SFL_REC_DEC_WORDS;
+  return 0;
+}
+
+// what every reader asks first: an evaluation handle with a recording armed and an evaluation behind the arming
+template <class B>
+int bank_record_check(Handle<B>* h, const char* fn) {
+  if (!h->bank.on) return fail(std::string(fn) + ": not an evaluation handle (sfl_create_eval)");
+  if (!h->bank.rec_n) return fail(std::string(fn) + ": no recording armed (sfl_bank_record)");
+  if (!h->bank.recorded) return fail(std::string(fn) + ": no successful sfl_bank_eval since the recording was armed");
+  return 0;
+}
+
+template <class B>
+int bank_record_counts(Handle<B>* h, int32_t* ticks, int32_t* decisions) {
+  if (int rc = bank_record_check(h, "sfl_bank_record_counts")) return rc;
+  typename Handle<B>::Bank& bk = h->bank;
+  // the evaluation's own per-env outputs, copied whole (one copy each) and indexed at the listed envs on the host
+  std::vector<int32_t> t(ticks ? h->E : 0), d(decisions ? h->E : 0);
+  if (ticks) h->be.d2h_async(t.data(), bk.ticks, (size_t)h->E * 4);
+  if (decisions) h->be.d2h_async(d.data(), bk.dec, (size_t)h->E * 4);
+  if (h->be.sync()) return fail(h->be.error());
+  for (uint32_t k = 0; k < bk.rec_n; ++k) {
+    if (ticks) ticks[k] = t[bk.rec_env[k]];
+    if (decisions) decisions[k] = d[bk.rec_env[k]];
+  }
+  return 0;
+}
+
+template <class B>
+int bank_record_read(Handle<B>* h, uint32_t k, int32_t* cell, uint32_t* bits, int32_t* dec) {
+  if (int rc = bank_record_check(h, "sfl_bank_record_read")) return rc;
+  typename Handle<B>::Bank& bk = h->bank;
+  if (k >= bk.rec_n) return fail("sfl_bank_record_read: slot " + std::to_string(k) + " of " + std::to_string(bk.rec_n));
+  const size_t nf = (size_t)bk.rec_tick_cap * (size_t)h->map.T, nr = (size_t)bk.rec_dec_cap * SFL_REC_DEC_WORDS;
+  if (cell) h->be.d2h_async(cell, bk.rec_cell + (size_t)k * nf, nf * 4);
+  if (bits) h->be.d2h_async(bits, bk.rec_bits + (size_t)k * nf, nf * 4);
+  if (dec) h->be.d2h_async(dec, bk.rec_rows + (size_t)k * nr, nr * 4);
+  return h->be.sync() ? fail(h->be.error()) : 0;
+}
+
+template <class B>
+int bank_record_traffic(Handle<B>* h, uint32_t p, sfl_record_traffic* out) {
+  if (int rc = bank_record_check(h, "sfl_bank_record_traffic")) return rc;
+  typename Handle<B>::Bank& bk = h->bank;
+  if (p >= bk.P) return fail("sfl_bank_record_traffic: policy " + std::to_string(p) + " of " + std::to_string(bk.P));
+  if (!out) return fail("sfl_bank_record_traffic: null argument");
+  const size_t HW = (size_t)h->map.HW, S = (size_t)h->map.lrn.S;
+  RecArgs a{};
+  a.n = bk.rec_n;
+  a.E = h->E;
+  a.HW = (uint32_t)HW;
+  a.S = (uint32_t)S;
+  a.T = h->map.T;
+  a.tick_cap = bk.rec_tick_cap;
+  a.dec_cap = bk.rec_dec_cap;
+  a.p = p;
+  a.env = bk.rec_env_d;
+  a.policy = bk.policy;
+  a.ticks = bk.ticks;
+  a.dec = bk.dec;
+  a.cell = bk.rec_cell;
+  a.bits = bk.rec_bits;
+  a.rows = bk.rec_rows;
+  a.sw_na = h->map.sw_na;
+  a.out = bk.rec_out;
+  int rc = h->be.rec_traffic(a);  // (timed on its own: elapsed_ms after the sync below)
+  if (!rc) {
+    if (out->occupancy) h->be.d2h_async(out->occupancy, bk.rec_out, HW * 4);
+    if (out->standing) h->be.d2h_async(out->standing, bk.rec_out + HW, HW * 4);
+    if (out->standing_malfunction) h->be.d2h_async(out->standing_malfunction, bk.rec_out + 2 * HW, HW * 4);
+    if (out->decisions) h->be.d2h_async(out->decisions, bk.rec_out + 3 * HW, S * 4);
+    if (out->stops) h->be.d2h_async(out->stops, bk.rec_out + 3 * HW + S, S * 4);
+    rc = h->be.sync();
+  }
+  if (rc) return fail(std::string("sfl_bank_record_traffic: ") + h->be.error());
+  bk.rc_last_ms = h->be.elapsed_ms();
+  bk.rc_total_ms += bk.rc_last_ms;
+  return 0;
 }
 
 // ---------------------------------------------------------------------------

@@ -107,6 +107,11 @@ struct HostBackend {
     sfl::diag_fold_host(a);
     return 0;
   }
+  // sfl_bank_record_traffic: the fold as plain loops (sfl_rec.h)
+  int rec_traffic(const sfl::RecArgs& a) {
+    sfl::rec_traffic_host(a);
+    return 0;
+  }
   // sfl_state_*: one phase as plain loops (sfl_snap.h)
   int snap(const sfl::SnapArgs& a, int phase, float* ms) {
     sfl::snap_host(a, phase);

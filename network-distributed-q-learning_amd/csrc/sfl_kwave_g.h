@@ -72,6 +72,24 @@ k_wave_g_bank(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict
   sfl::wave::run_groups<PPL, SPL, TW, false, G, false, LM, false, false, true>(*m, *s, *c);
 }
 
+// BANK with a recording armed (sfl_bank_record; sfl_wave.h REC): kernels of their own again, launched only while a
+// recording is armed, so that the evaluation without one runs the kernels above unchanged
+template <int PPL, int SPL, int TW>
+__global__ void __launch_bounds__(SFL_WAVE_BLOCK) __attribute__((amdgpu_waves_per_eu(SFL_WAVE_OCC)))
+k_wave_bank_rec(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict__ s, const sfl::SflCtl* __restrict__ c) {
+  sfl::wave::run<PPL, SPL, TW, false, false, false, false, false, true, true>(*m, *s, *c);
+}
+template <int PPL, int SPL, int TW>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SFL_WAVE2_OCC)))
+k_wave2_bank_rec(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict__ s, const sfl::SflCtl* __restrict__ c) {
+  sfl::wave::run<PPL, SPL, TW, false, false, false, false, false, true, true>(*m, *s, *c);
+}
+template <int PPL, int SPL, int TW, int G, int OCC, bool LM>
+__global__ void __launch_bounds__(SFL_GROUP_BLOCK) __attribute__((amdgpu_waves_per_eu(OCC)))
+k_wave_g_bank_rec(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict__ s, const sfl::SflCtl* __restrict__ c) {
+  sfl::wave::run_groups<PPL, SPL, TW, false, G, false, LM, false, false, true, true>(*m, *s, *c);
+}
+
 // ---- one launch path from the shape table ---------------------------------------------------------------------
 // A cell = a row v of sfl::kVariants (1 .. kNumVariants - 1) x a launch mode.  Everything about a cell follows from
 // the row: its kernel family, its grid and block, and the translation unit that compiles it.
@@ -81,7 +99,8 @@ static_assert(sizeof(sfl::kVariants) / sizeof(sfl::kVariants[0]) == sfl::kNumVar
 // Bank: an evaluation handle's episode launch (sfl_bank_eval) -- every row, the LM one with a cell of its own (a
 // launch is a whole episode, hundreds of decisions per env, which is what the copy of the tables into LDS pays for;
 // external-action mode's single decision per launch is not)
-enum class Mode { Plain, Trace, Timed, Hpg, Ext, Bank };
+// BankRec: the same launch with a recording armed (sfl_bank_record): every row again
+enum class Mode { Plain, Trace, Timed, Hpg, Ext, Bank, BankRec };
 // libsfl.so's translation units (build.TUS): sfl.hip, sfl_kwave_v7.hip, sfl_kwave_hpg.hip, sfl_kwave_hpg_v7.hip,
 // sfl_kwave_ext.hip, sfl_kwave_bank.hip
 enum class Unit { Main, V7, Hpg, HpgV7, Ext, Bank };
@@ -90,7 +109,7 @@ constexpr int kSchedVariant = 7;  // the bench's c3 shape: its units are built w
 // exactly one owner (this function's value); a unit that does not define its launch_unit fails the link.
 constexpr Unit owner(int v, Mode md) {
   if (md == Mode::Ext) return Unit::Ext;
-  if (md == Mode::Bank) return Unit::Bank;
+  if (md == Mode::Bank || md == Mode::BankRec) return Unit::Bank;
   if (md == Mode::Hpg) return v == kSchedVariant ? Unit::HpgV7 : Unit::Hpg;
   return v == kSchedVariant ? Unit::V7 : Unit::Main;
 }
@@ -124,6 +143,13 @@ inline void launch_cell(const Launch& l) {
         k_wave2_bank<w.PPL, w.SPL, w.TW><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
       else
         k_wave_bank<w.PPL, w.SPL, w.TW><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
+    } else if constexpr (MD == Mode::BankRec) {
+      if constexpr (w.G < 64)
+        k_wave_g_bank_rec<w.PPL, w.SPL, w.TW, w.G, w.OCC, (bool)w.LM><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
+      else if constexpr (two_slot(w))
+        k_wave2_bank_rec<w.PPL, w.SPL, w.TW><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
+      else
+        k_wave_bank_rec<w.PPL, w.SPL, w.TW><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
     } else if constexpr (EXT && w.LM)
       return;  // (no such cell: ext_variant maps the row to its twin)
     else if constexpr (w.G < 64)
@@ -137,7 +163,8 @@ inline void launch_cell(const Launch& l) {
 template <Unit U, int... I>
 inline void launch_owned(const Launch& l, std::integer_sequence<int, I...>) {
   ((launch_cell<U, I + 1, Mode::Plain>(l), launch_cell<U, I + 1, Mode::Trace>(l), launch_cell<U, I + 1, Mode::Timed>(l),
-    launch_cell<U, I + 1, Mode::Hpg>(l), launch_cell<U, I + 1, Mode::Ext>(l), launch_cell<U, I + 1, Mode::Bank>(l)), ...);
+    launch_cell<U, I + 1, Mode::Hpg>(l), launch_cell<U, I + 1, Mode::Ext>(l), launch_cell<U, I + 1, Mode::Bank>(l),
+    launch_cell<U, I + 1, Mode::BankRec>(l)), ...);
 }
 // a unit's launches: declared here, defined (SFL_KWAVE_UNIT) in the unit itself
 template <Unit U>

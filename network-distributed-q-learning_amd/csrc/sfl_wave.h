@@ -1846,7 +1846,8 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     uint32_t amask = 0;  // EXT: the action mask of an emitted observation
   };
   struct DecNone {};
-  struct Dec : std::conditional<EXT, DecExt, DecNone>::type {  // (a driver starts from the zero record: no decision in flight)
+  // (BANK: the mask too, for a recorded env's decision row -- rec_decide() right behind decide())
+  struct Dec : std::conditional<EXT || BANK, DecExt, DecNone>::type {  // (a driver starts from the zero record: no decision in flight)
     int sw = 0, h = 0, slot = 0;
     uint32_t state = 0;
     int action = 0, j = 0;
@@ -2222,6 +2223,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     d.j = (action == stop) ? (w - 1) : swr.j(action);
     d.reward = reward;
     d.next_sw = next_sw;
+    if constexpr (BANK) d.amask = amask;
     d.abytes = 220u + 48u * (uint32_t)np + 8u * (uint32_t)na;  // SURVEY.md §8(d) bytes of this decision
     return false;
   }
@@ -2537,6 +2539,43 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     }
   }
 
+  // BANK: the armed recording (SflCtl::rec_*; include/sfl.h sfl_bank_record).  The REC drivers -- the instantiation an
+  // evaluation with a recording armed launches -- ask rec_slot() behind a tick, a decision and a post: a load of the
+  // env's slot index (group-uniform; nothing of the recording is held in a register across the loop), and a recorded
+  // env then writes: after tick `now` its frame, each train's cell and masked tr_bits word from the lane that holds the
+  // train slot (T consecutive words per array, plain vector stores); behind decide() the first nine words of decision
+  // ep_dec's row from the env's lane 0, at its post the tenth.  Ticks past rec_tick_cap and decisions past
+  // rec_dec_cap are dropped.
+  __device__ __forceinline__ int32_t rec_slot(const SflCtl& c) const { return c.rec_slot ? U(ld(c.rec_slot, (size_t)e)) : -1; }
+  __device__ __forceinline__ void rec_tick(const SflCtl& c, int32_t slot) {
+    if (now > c.rec_tick_cap) return;
+    const size_t f = ((size_t)slot * (size_t)c.rec_tick_cap + (size_t)(now - 1)) * (size_t)m.T;
+#pragma unroll
+    for (int k = 0; k < TPL; ++k) {
+      if (mine[k]) {
+        st(c.rec_cell, f + (size_t)(lid() + G * k), pos[k]);
+        st(c.rec_bits, f + (size_t)(lid() + G * k), bits[k] & REC_BITS_MASK);
+      }
+    }
+  }
+  __device__ __forceinline__ void rec_decide(const SflCtl& c, int32_t slot, const Dec& d) {
+    if (lid() != 0 || ep_dec >= c.rec_dec_cap) return;
+    const size_t r = ((size_t)slot * (size_t)c.rec_dec_cap + (size_t)ep_dec) * REC_DEC_WORDS;
+    st(c.rec_dec, r + REC_NOW, (int32_t)now);
+    st(c.rec_dec, r + REC_SWITCH, (int32_t)d.sw);
+    st(c.rec_dec, r + REC_TRAIN, (int32_t)d.h);
+    st(c.rec_dec, r + REC_SLOT, (int32_t)d.slot);
+    st(c.rec_dec, r + REC_STATE, (int32_t)d.state);
+    st(c.rec_dec, r + REC_MASK, (int32_t)d.amask);
+    st(c.rec_dec, r + REC_ACTION, (int32_t)d.action);
+    st(c.rec_dec, r + REC_REWARD, (int32_t)d.reward);
+    st(c.rec_dec, r + REC_NEXT_SWITCH, (int32_t)d.next_sw);
+  }
+  __device__ __forceinline__ void rec_post(const SflCtl& c, int32_t slot) {  // (before count_decision: ep_dec is the row)
+    if (lid() != 0 || ep_dec >= c.rec_dec_cap) return;
+    st(c.rec_dec, ((size_t)slot * (size_t)c.rec_dec_cap + (size_t)ep_dec) * REC_DEC_WORDS + REC_STEP_NOW, (int32_t)now);
+  }
+
   // ---- external-action mode (EXT): env_run_ext of sfl_core.h, operation for operation, for both drivers -------
   // One launch = one call of sfl_env_step: the env applies the caller's action to the observation the last launch
   // emitted, runs on to its next observation (or its episode's end) and stops there.  A flat loop like
@@ -2693,11 +2732,14 @@ struct PhaseTimer {
 // EXT: one call of external-action mode (WEnv::ext_run; c.ext = the call's SflExt)
 // BANK: one greedy episode on the env's table of the policy bank (sfl_bank_eval): the launch starts at PH_RESET and
 // the env stops at its episode's end, where bank_end() writes its outputs
+// REC (BANK only): the instantiation an evaluation with a recording armed launches (SflCtl::rec_*); the one without
+// it carries none of the recording's code, so an evaluation with no recording armed runs what it ran before
 template <int PPL, int SPL, int TW, bool TRACE, bool PART = false, bool TIMED = false, bool HPG = false, bool EXT = false,
-          bool BANK = false>
+          bool BANK = false, bool REC = false>
 __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const SflPart* P = nullptr) {
   static_assert(!(EXT && (TRACE || TIMED)), "external-action mode: no trace, no phase timers");
   static_assert(!(BANK && (TRACE || TIMED)), "policy-bank evaluation: no trace, no phase timers");
+  static_assert(BANK || !REC, "a recording is a policy-bank evaluation's");
   using V = WEnv<PPL, SPL, TW, PART, 64, false, HPG, EXT, BANK>;
   // semaphores, counters, prefetch records, rng, timetable (PART: one record, timetable from the map)
   // (PART: the launch's initial records / counters in place of the timetable copy)
@@ -2753,6 +2795,10 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
       abytes += 36u * (uint32_t)(m.T - mpopc(v.arr_mask));
       if constexpr (TIMED) tm.lap(TM_OTHER);
       v.tick();
+      if constexpr (REC) {  // a recorded env's frame of this tick
+        const int32_t rs = v.rec_slot(c);
+        if (rs >= 0) v.rec_tick(c, rs);
+      }
       if constexpr (TIMED) tm.lap(TM_TICK);
       ticks++;
       phase = v.after_tick();
@@ -2764,6 +2810,10 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
         v.post(d, greedy);
         if constexpr (TIMED) tm.lap(TM_POST);
         if (TRACE && c.trace && (int32_t)e == c.trace_env) v.trace_decision(c, d, lane);
+        if constexpr (REC) {  // a recorded env's row: when the step returned
+          const int32_t rs = v.rec_slot(c);
+          if (rs >= 0) v.rec_post(c, rs);
+        }
         v.count_decision(d, max_steps);
         phase = v.after_post();
         return dec_budget > 0 && dec_base + (int64_t)v.n_dec >= dec_budget;
@@ -2787,6 +2837,10 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
           if (PART && requested) {
             stop = true;  // the round ends at the request (phase stays PH_DECIDE)
             break;
+          }
+          if constexpr (REC) {  // a recorded env's row: the observation and the applied action
+            const int32_t rs = v.rec_slot(c);
+            if (rs >= 0) v.rec_decide(c, rs, d);
           }
           abytes += d.abytes;
           v.flags |= F_INFLIGHT;
@@ -2854,10 +2908,11 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
 // one post step and one decision.  The groups of a wave diverge (one ticks while another decides);
 // a batch loop as in run() would hold every group until the longest batch of the wave is done.
 template <int PPL, int SPL, int TW, bool TRACE, int G, bool TIMED = false, bool LM = false, bool HPG = false, bool EXT = false,
-          bool BANK = false>
+          bool BANK = false, bool REC = false>
 __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) {
   static_assert(!(EXT && (TRACE || TIMED)), "external-action mode: no trace, no phase timers");
   static_assert(!(BANK && (TRACE || TIMED)), "policy-bank evaluation: no trace, no phase timers");
+  static_assert(BANK || !REC, "a recording is a policy-bank evaluation's");
   using V = WEnv<PPL, SPL, TW, false, G, LM, HPG, EXT, BANK>;
   // per env: semaphores, counters, prefetch records, rng; per block: the timetable rows and the
   // per-switch / per-port map records (the groups of a wave read different switches' records: LDS
@@ -2953,6 +3008,10 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
     if (phase == PH_TICK && !wave_decides) {
       abytes += 36u * (uint32_t)(m.T - mpopc(v.arr_mask));
       v.tick();
+      if constexpr (REC) {  // a recorded env's frame of this tick
+        const int32_t rs = v.rec_slot(c);
+        if (rs >= 0) v.rec_tick(c, rs);
+      }
       ticks++;
       phase = v.after_tick();
     }
@@ -2961,6 +3020,10 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
       const bool greedy = BANK || (v.flags & F_GREEDY) != 0;
       v.post(d, greedy);
       if (TRACE && c.trace && (int32_t)e == c.trace_env) v.trace_decision(c, d, v.lane);
+      if constexpr (REC) {  // a recorded env's row: when the step returned
+        const int32_t rs = v.rec_slot(c);
+        if (rs >= 0) v.rec_post(c, rs);
+      }
       v.count_decision(d, max_steps);
       phase = v.after_post();
       if (v.n_dec >= dec_budget) break;
@@ -2973,6 +3036,10 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
     if (phase == PH_DECIDE) {
       const bool greedy = BANK || (v.flags & F_GREEDY) != 0;
       v.template decide<TIMED>(d, greedy);
+      if constexpr (REC) {  // a recorded env's row: the observation and the applied action
+        const int32_t rs = v.rec_slot(c);
+        if (rs >= 0) v.rec_decide(c, rs, d);
+      }
       abytes += d.abytes;
       v.flags |= F_INFLIGHT;
       phase = many(v.q_mask) ? PH_POST : PH_TICK;

@@ -219,9 +219,16 @@ class DistrQLearning:
         return int(el[0]), int(ph[0]), sem, pos, bits
 
     def test(self, out_dir, plot=False, save_outputs=True):
-        """distr_q.py:184-241: one greedy episode per env; returns (cum_reward, arrived, delays)."""
+        """distr_q.py:184-241: one greedy episode per env; returns (cum_reward, arrived, delays).  ``plot`` (a one-env
+        learner): the episode again on a one-env ``runtime.EvalBatch`` with the same table and seed and a recording
+        armed, rendered after every decision into ``out_dir/iter_<n>.png`` (distr_q.py:216-221)."""
+        if plot and self.batch.E != 1:
+            raise NotImplementedError("test(plot=True) renders a one-env learner; record chosen envs of a batch with "
+                                      "runtime.EvalBatch.record and render them with render.frames_at_decisions")
         t0 = time.time()
         out = self.batch.test(1)
+        if plot:
+            self._plot_episode(out_dir, float(out["cum_reward"][0][0]), int(out["decisions"][0][0]))
         cum = self._squeeze(out["cum_reward"][0])
         arrived = self._squeeze(out["arrived"][0])
         delays = out["delays"][0].T.astype(np.float64)  # [E, T]
@@ -237,6 +244,26 @@ class DistrQLearning:
             self._save(out_dir, "delays.npz", delays)
         self._timing(t0)
         return cum, arrived, delays
+
+    def _plot_episode(self, out_dir, cum, decisions):
+        """The test episode once more with a recorder on it (the bank episode starts from a reset and is the same
+        greedy episode: its cum_reward must be the test's), one PNG per decision."""
+        from . import render
+        b = self.batch
+        ev = runtime.EvalBatch(b.cm, self.hp, [b.seeds[0]], 1, lib=b.lib, device=self.env.device,
+                               max_steps=self.env.max_steps, malfunction_stream=b.malfunction_stream,
+                               delay_threshold=getattr(self.env, "delay_threshold", 20))
+        try:
+            ev.set_policy_raw(0, *b.q_raw(0))
+            ev.record([0], max_decisions=max(decisions, 1))
+            got = ev.evaluate([0])
+            assert float(got["cum_reward"][0]) == cum and int(got["decisions"][0]) == decisions, \
+                "the recorded episode is not the test episode"
+            ep = ev.recording(0)
+        finally:
+            ev.close()
+        for n, img in enumerate(render.frames_at_decisions(b.cm, ep)):
+            render.save_png(os.path.join(out_dir, f"iter_{n}.png"), img)
 
     def consensus_table(self, mode: str = "mean", cohorts: Optional[Sequence[Optional[int]]] = None,
                         share: bool = False) -> Dict[tuple, list]:

@@ -177,6 +177,24 @@ class ASyncSwitchEnv:
         """The port reservation table of env 0 in the reference's format (rail_network.semaphores)."""
         return self._aec.semaphores(0)
 
+    def render(self):
+        """switch_env.py's render(): None without a ``render_mode``; otherwise the RGB array (uint8 [H * 8][W * 8][3],
+        render.frame) of the trains as they stand now, from the device's env state.  ``"human"`` opens no window here
+        and returns the array too."""
+        if self.render_mode is None:
+            return None
+        aec = getattr(self, "_aec", None)
+        if aec is None:
+            raise RuntimeError("render(): reset() the env first")
+        from . import render as render_mod
+        from .parity import env_state
+        from .runtime import Episode
+        _, _, _, pos, bits = env_state(aec.batch, 0)
+        b = np.asarray(bits, np.uint32)[None, :]
+        now = Episode(0, self._aec_seed, 0, 1, 0, 1, 1, np.asarray(pos, np.int32)[None, :], (b & 3).astype(np.uint8),
+                      ((b >> 2) & 7).astype(np.uint8), ((b >> 13) & 0xFF).astype(np.uint8), {})
+        return render_mod.frame(self.compiled, now, 0)
+
     def get_num_agents(self) -> int:
         return self.compiled.T
 

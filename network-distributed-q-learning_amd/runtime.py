@@ -790,6 +790,10 @@ class EvalBatch:
         self.seeds = [int(s) for s in seeds]
         self.E = len(self.seeds)
         self.P = int(n_policies)
+        self.max_steps = int(max_steps)
+        self._rec_envs: List[int] = []
+        self._rec_counts: Optional[Tuple[np.ndarray, np.ndarray]] = None  # (of the last evaluate, fetched once)
+        self._policy: Optional[np.ndarray] = None
         self.lib = lib or _lib.load_product()
         if self.P < 0 or self.P > 0xFFFFFFFF:
             raise ValueError("EvalBatch: n_policies out of range")
@@ -889,6 +893,8 @@ class EvalBatch:
         self.lib.check(self.lib.dll.sfl_bank_read(self.h, _ptr(cells, C.c_int64)), "sfl_bank_read")
         out["policy"] = pol
         out["table"] = eval_table(cells)
+        self._policy = pol
+        self._rec_counts = None
         return out
 
     def fold_ms(self) -> Tuple[float, float]:
@@ -941,6 +947,141 @@ class EvalBatch:
         last, total = C.c_double(0.0), C.c_double(0.0)
         self.lib.check(self.lib.dll.sfl_bank_diag_ms(self.h, C.byref(last), C.byref(total)), "sfl_bank_diag_ms")
         return float(last.value), float(total.value)
+
+
+    # ---- episodes recorded on the device ----
+    def record(self, envs: Optional[Sequence[int]], max_ticks: Optional[int] = None,
+               max_decisions: Optional[int] = None) -> None:
+        """Arm a recording of the listed envs (distinct, any order; slot k is ``envs[k]``) for every later ``evaluate``
+        (include/sfl.h sfl_bank_record states what is recorded); ``None`` or an empty list disarms it.  ``max_ticks``
+        defaults to the map's ``max_episode_steps`` -- a tick at that horizon ends the episode, so no frame is cut --
+        and ``max_decisions`` to ``min(max_steps + 1, 4096)``."""
+        envs = [] if envs is None else [int(e) for e in envs]
+        self._rec_counts = None
+        if any(e < 0 or e > 0xFFFFFFFF for e in envs):
+            raise ValueError("record: env ids must be non-negative")
+        if not envs:
+            self.lib.check(self.lib.dll.sfl_bank_record(self.h, 0, None, 0, 0), "sfl_bank_record")
+            self._rec_envs = []
+            return
+        ticks = int(self.cm.scenario.max_episode_steps if max_ticks is None else max_ticks)
+        decs = int(min(self.max_steps + 1, 4096) if max_decisions is None else max_decisions)
+        if not (-2**31 <= ticks < 2**31 and -2**31 <= decs < 2**31):
+            raise ValueError("record: max_ticks / max_decisions out of range")
+        a = np.array(envs, dtype=np.uint32)
+        self.lib.check(self.lib.dll.sfl_bank_record(self.h, len(envs), _ptr(a, C.c_uint32), ticks, decs), "sfl_bank_record")
+        self._rec_envs = envs
+
+    def record_info(self) -> Dict[str, int]:
+        """The armed recording: ``n`` (0: none), ``tick_cap``, ``dec_cap``, ``dec_words``."""
+        o = _lib.RecordInfo()
+        self.lib.check(self.lib.dll.sfl_bank_record_info(self.h, C.byref(o)), "sfl_bank_record_info")
+        return dict(n=int(o.n), tick_cap=int(o.tick_cap), dec_cap=int(o.dec_cap), dec_words=int(o.dec_words))
+
+    def recording(self, k: int) -> "Episode":
+        """Slot ``k`` of the recording, as the last ``evaluate`` filled it: the episode of env ``record``'s ``envs[k]``."""
+        info = self.record_info()
+        n, T = info["n"], self.cm.T
+        if int(k) < 0 or int(k) > 0xFFFFFFFF:
+            raise ValueError("recording: slot out of range")
+        if self._rec_counts is None:  # (every slot's counts in one call, kept until the next evaluate / record)
+            ticks, decs = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+            self.lib.check(self.lib.dll.sfl_bank_record_counts(self.h, _ptr(ticks, C.c_int32), _ptr(decs, C.c_int32)),
+                           "sfl_bank_record_counts")
+            self._rec_counts = (ticks, decs)
+        ticks, decs = self._rec_counts
+        cell = np.zeros((info["tick_cap"], T), np.int32)
+        bits = np.zeros((info["tick_cap"], T), np.uint32)
+        rows = np.zeros((info["dec_cap"], info["dec_words"]), np.int32)
+        self.lib.check(self.lib.dll.sfl_bank_record_read(self.h, int(k), _ptr(cell, C.c_int32), _ptr(bits, C.c_uint32),
+                                                         _ptr(rows, C.c_int32)), "sfl_bank_record_read")
+        env = self._rec_envs[int(k)]
+        return Episode.from_raw(self.cm, env, self.seeds[env], int(self._policy[env]), int(ticks[k]), int(decs[k]),
+                                cell, bits, rows)
+
+    def traffic(self, p: int) -> Dict[str, np.ndarray]:
+        """The recorded frames and decisions of the slots whose env followed policy ``p`` in the last ``evaluate``,
+        reduced on the device (include/sfl.h sfl_bank_record_traffic): ``occupancy``, ``standing``,
+        ``standing_malfunction`` as [H][W] and ``decisions``, ``stops`` as [S] uint32 arrays."""
+        if int(p) < 0 or int(p) > 0xFFFFFFFF:
+            raise ValueError("traffic: policy id out of range")
+        H, W, S = self.cm.H, self.cm.W, self.cm.S
+        out = {k: np.zeros((H, W) if i < 3 else (S,), np.uint32) for i, k in enumerate(_lib.TRAFFIC_FIELDS)}
+        o = _lib.RecordTraffic()
+        for k in _lib.TRAFFIC_FIELDS:
+            setattr(o, k, _ptr(out[k], C.c_uint32))
+        self.lib.check(self.lib.dll.sfl_bank_record_traffic(self.h, int(p), C.byref(o)), "sfl_bank_record_traffic")
+        return out
+
+    def record_ms(self) -> Tuple[float, float]:
+        """Device ms of the last traffic fold and of all of this handle."""
+        last, total = C.c_double(0.0), C.c_double(0.0)
+        self.lib.check(self.lib.dll.sfl_bank_record_ms(self.h, C.byref(last), C.byref(total)), "sfl_bank_record_ms")
+        return float(last.value), float(total.value)
+
+
+class Episode:
+    """One recorded bank episode (``EvalBatch.recording``): ``env``, ``seed``, ``policy``; the episode's true ``ticks``
+    and ``n_decisions`` and ``complete`` (both within the recording's caps); the kept frames ``cell`` (int32, -1 off
+    the map), ``heading``, ``state`` (index into ``_lib.TRAIN_STATES``) and ``malfunction`` (the counter) as
+    [frames][T], frame i after tick i + 1; and ``decisions``: one [rows] int array per field of
+    ``_lib.REC_DEC_FIELDS`` plus ``obs`` ([rows] observation tuples, ``CompiledMap.obs_of_row``) and ``agent`` (the
+    deciding switches' names)."""
+
+    def __init__(self, env, seed, policy, ticks, n_decisions, tick_cap, dec_cap, cell, heading, state, malfunction,
+                 decisions):
+        self.env, self.seed, self.policy = int(env), int(seed), int(policy)
+        self.ticks, self.n_decisions = int(ticks), int(n_decisions)
+        self.tick_cap, self.dec_cap = int(tick_cap), int(dec_cap)
+        self.cell, self.heading, self.state, self.malfunction = cell, heading, state, malfunction
+        self.decisions = decisions
+
+    @property
+    def complete(self) -> bool:
+        return self.ticks <= self.tick_cap and self.n_decisions <= self.dec_cap
+
+    @property
+    def frames(self) -> int:
+        return int(self.cell.shape[0])
+
+    @property
+    def rows(self) -> int:
+        return int(self.decisions["now"].shape[0])
+
+    @classmethod
+    def from_raw(cls, cm: CompiledMap, env, seed, policy, ticks, n_decisions, cell, bits, rows) -> "Episode":
+        """From a slot's arrays as sfl_bank_record_read returns them ([tick_cap][T], [tick_cap][T], [dec_cap][words]):
+        cut to the kept frames and rows, the state word taken apart, the observations decoded."""
+        nf, nr = min(ticks, cell.shape[0]), min(n_decisions, rows.shape[0])
+        b = bits[:nf]
+        dec = {k: np.ascontiguousarray(rows[:nr, i]) for i, k in enumerate(_lib.REC_DEC_FIELDS)}
+        dec["obs"] = [cm.obs_of_row(int(s), int(sl), int(st)) for s, sl, st in zip(dec["switch"], dec["slot"], dec["state"])]
+        dec["agent"] = ["switch_%d-%d" % tuple(cm.switch_ids[int(s)]) for s in dec["switch"]]
+        return cls(env, seed, policy, ticks, n_decisions, cell.shape[0], rows.shape[0], np.ascontiguousarray(cell[:nf]),
+                   (b & 3).astype(np.uint8), ((b >> 2) & 7).astype(np.uint8), ((b >> 13) & 0xFF).astype(np.uint8), dec)
+
+    def save(self, path) -> None:
+        """One ``.npz``: the scalars, the frame arrays, the decision fields, the observation tuples (padded to the
+        longest, with their lengths) and the agents' names."""
+        meta = np.array([self.env, self.seed, self.policy, self.ticks, self.n_decisions, self.tick_cap, self.dec_cap],
+                        np.int64)
+        obs = self.decisions["obs"]
+        olen = np.array([len(o) for o in obs], np.int32)
+        opad = -np.ones((len(obs), int(olen.max()) if len(obs) else 0), np.int32)
+        for i, o in enumerate(obs):
+            opad[i, :len(o)] = o
+        np.savez_compressed(path, meta=meta, cell=self.cell, heading=self.heading, state=self.state,
+                            malfunction=self.malfunction, obs=opad, obs_len=olen,
+                            agent=np.array(self.decisions["agent"], dtype=np.str_),
+                            **{"dec_" + k: self.decisions[k] for k in _lib.REC_DEC_FIELDS})
+
+    @classmethod
+    def load(cls, path) -> "Episode":
+        with np.load(path) as z:
+            dec = {k: z["dec_" + k] for k in _lib.REC_DEC_FIELDS}
+            dec["obs"] = [tuple(int(x) for x in row[:n]) for row, n in zip(z["obs"], z["obs_len"])]
+            dec["agent"] = [str(x) for x in z["agent"]]
+            return cls(*[int(x) for x in z["meta"]], z["cell"], z["heading"], z["state"], z["malfunction"], dec)
 
 
 # include/sfl.h SFL_DIAG_*: the class a diagnosis gives a train, by value

@@ -3,14 +3,15 @@ k_wave / k_wave2 / k_wave_g / k_wave_part / k_wave2_part instantiation, matched 
 trailing HPG = false argument (the hyperparameter-group switch, csrc/sfl_kwave_g.h) is dropped, so a library with it
 compares against one from before it; HPG = true kernels are listed on their own.  Likewise the EXT argument behind it
 (external-action mode's kernels, sfl_env_begin_wave).  The policy-bank evaluation's kernels (k_wave_bank, k_wave2_bank,
-k_wave_g_bank: sfl_bank_eval) are listed as "BANK " + the key of their Plain twin, and a second table puts each beside
+k_wave_g_bank: sfl_bank_eval) are listed as "BANK " + the key of their Plain twin (those of an evaluation with a
+recording armed, k_wave*_bank_rec, as "BANKREC " + that key), and a second table puts each beside
 that twin.  The "code" column says whether the
 kernel's machine code (the symbol's bytes in its code object's .text) is the same in both, or the same but for
 pc-relative addresses (same_code).  Exit status 1 if a kernel
 present in both differs in a resource field (registers, spills, scratch, LDS); code bytes alone do not fail.  The
 transition assembler's kernels (k_trans_count, k_trans_write: sfl_trans.hip) are listed by name, and so are the cell
 folds and their reset kernels (k_curve_*: sfl_curve.hip; k_eval_*: sfl_eval.hip) and the non-arrival diagnosis's
-kernels (k_diag_*: sfl_diag.hip).
+kernels (k_diag_*: sfl_diag.hip) and the recordings' traffic fold (k_rec_*: sfl_rec.hip).
 Usage: python scripts/kres_diff.py OLD.so NEW.so [--md]"""
 import re
 import struct
@@ -66,20 +67,22 @@ def kernels_of(co):
     for blk in notes.split("- .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", blk).group(1)
         # (Itanium mangling: k_waveILi8ELi2ELb1E...E -- integer and bool template arguments only)
-        m = re.search(r"\d+(k_wave_g_bank|k_wave2_bank|k_wave_bank|k_wave_g|k_wave2_part|k_wave_part|k_wave2|k_wave)I((?:L[ib]\d+E)+)E", name)
+        m = re.search(r"\d+(k_wave_g_bank_rec|k_wave2_bank_rec|k_wave_bank_rec|k_wave_g_bank|k_wave2_bank|k_wave_bank|k_wave_g|k_wave2_part|k_wave_part|k_wave2|k_wave)I((?:L[ib]\d+E)+)E", name)
         if not m:
             # the transition assembler's kernels (sfl_trans.hip) and the cell folds with their reset kernels
             # (sfl_curve.hip, sfl_eval.hip): no template arguments, listed by name
-            t = re.search(r"\d+(k_(?:trans|curve|eval|diag)_[a-z_]+)", name)
+            t = re.search(r"\d+(k_(?:trans|curve|eval|diag|rec)_[a-z_]+)", name)
             if t:
                 vals = [int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in FIELDS]
                 out[t.group(1)] = vals + [size.get(name, -1), code.get(name)]
             continue
         args = [("true" if v == "1" else "false") if t == "b" else v for t, v in re.findall(r"L([ib])(\d+)E", m.group(2))]
         vals = [int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in FIELDS]
-        if m.group(1).endswith("_bank"):  # <PPL,SPL,TW[,G,OCC,LM]>: the key of the Plain twin (TRACE, TIMED false)
+        if m.group(1).endswith(("_bank", "_bank_rec")):  # <PPL,SPL,TW[,G,OCC,LM]>: the key of the Plain twin (TRACE, TIMED false)
             twin = args[:3] + ["false"] + (args[3:5] + ["false", args[5]] if len(args) == 6 else ["false"])
-            out["BANK " + m.group(1)[:-5] + "<" + ",".join(twin) + ">"] = vals + [size.get(name, -1), code.get(name)]
+            rec = m.group(1).endswith("_rec")  # (the kernels of an evaluation with a recording armed: listed on their own)
+            out[("BANKREC " if rec else "BANK ") + m.group(1)[:-9 if rec else -5] + "<" + ",".join(twin) + ">"] = \
+                vals + [size.get(name, -1), code.get(name)]
             continue
         full = {"k_wave": 6, "k_wave2": 6, "k_wave_g": 9}.get(m.group(1))  # (the part kernels have no HPG argument)
         # (a trailing EXT argument behind HPG: external-action mode's kernels, listed on their own like HPG's)
