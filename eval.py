@@ -13,6 +13,9 @@ not arrive is classified on the device as well (eval_batch/nonarrivals.json); wi
 experiment are recorded on the device in a second, identical evaluation -- with --diagnose the first K whose env has a
 stalled train (classes 4 - 6), otherwise the first K -- and written as eval_batch/episode_<seed>.npz
 (runtime.Episode) beside eval_batch/traffic.npz, and with --frames rendered into eval_batch/frames_<seed>/iter_<n>.png.
+With --train-pool each table is also scored on the N seeds episode_seed(random_seed, 0 .. N - 1) of its own training pool
+(the [MISC] seed_pool of its config, which must not be 1): eval_batch/train_pool.json and per_env_train_pool.npz; its
+table beside summary.json's, on fresh seeds, is the generalisation gap.
 """
 import argparse
 import configparser
@@ -28,7 +31,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 PKG = "network-distributed-q-learning_amd"
 ASyncSwitchEnv = importlib.import_module(PKG + ".env").ASyncSwitchEnv
 DistrQLearning = importlib.import_module(PKG + ".distr_q").DistrQLearning
-from main import build_scenario  # noqa: E402
+from main import build_scenario, seed_schedule  # noqa: E402
 
 
 def evaluate(exp_dirs, model_file="distr_q_model.pkl", lib=None):
@@ -45,7 +48,8 @@ def evaluate(exp_dirs, model_file="distr_q_model.pkl", lib=None):
         model = DistrQLearning(env=env, gamma=float(m["gamma"]), epsilon=float(m["epsilon"]),
                                epsilon_decay_rate=float(m["epsilon_decay_rate"]), lr=float(m["lr"]),
                                lr_decay_rate=float(m["lr_decay_rate"]), default_q=float(m["default_q"]),
-                               seed=int(config["MISC"]["random_seed"]), lib=lib)
+                               seed=int(config["MISC"]["random_seed"]), lib=lib,
+                               **dict(zip(("seed_pool", "heldout_exploit"), seed_schedule(config))))
         model.load(os.path.join(exp_dir, model_file))
         num_evals = 10 if float(config["ENV"].get("malfunction_rate", 0)) > 0 else 1
         runs = []
@@ -69,7 +73,7 @@ def _scenario_key(config):
 
 
 def evaluate_batch(exp_dirs, n_envs, model_file="distr_q_model.pkl", seed0=None, lib=None, diagnose=False, stall=30,
-                   record=0, frames=False):
+                   record=0, frames=False, train_pool=False):
     """Each experiment's saved Q-table on ``n_envs`` greedy episodes, env i on seed ``seed0 + i`` (default ``seed0``:
     the experiment's ``random_seed``), in one device batch per group of experiments on the same scenario: the group's
     tables are the policies of one ``runtime.EvalBatch`` of ``len(group) * n_envs`` envs.  Experiments share a scenario
@@ -86,7 +90,12 @@ def evaluate_batch(exp_dirs, n_envs, model_file="distr_q_model.pkl", seed0=None,
     (``EvalBatch.record``): with ``diagnose`` the first K envs that have a train of class 4 - 6, otherwise the first K.
     ``EXP_DIR/eval_batch/episode_<seed>.npz`` holds each (``runtime.Episode.load``), ``traffic.npz`` the experiment's
     recorded traffic (``EvalBatch.traffic``) and the recorded seeds; ``frames`` also renders every recorded decision
-    into ``EXP_DIR/eval_batch/frames_<seed>/iter_<n>.png``.  Without ``record`` every file is what it is today."""
+    into ``EXP_DIR/eval_batch/frames_<seed>/iter_<n>.png``.  Without ``record`` every file is what it is today.
+    With ``train_pool`` a further evaluation scores each table on the ``n_envs`` seeds ``runtime.episode_seed(random_seed,
+    0 .. n_envs - 1)`` of its own training pool and writes ``EXP_DIR/eval_batch/train_pool.json`` (the summary's form)
+    and ``per_env_train_pool.npz``; the returned summary gets the key ``train_pool``.  Refused (``ValueError``, before
+    anything runs) when an experiment's config has no ``[MISC] seed_pool`` other than 1: it was trained on one
+    scenario.  The other files are what they are without it."""
     runtime = importlib.import_module(PKG + ".runtime")
     n_envs = int(n_envs)
     if n_envs < 1:
@@ -95,6 +104,9 @@ def evaluate_batch(exp_dirs, n_envs, model_file="distr_q_model.pkl", seed0=None,
     for exp_dir in exp_dirs:
         config = configparser.ConfigParser()
         config.read(os.path.join(exp_dir, "config.ini"))
+        if train_pool and seed_schedule(config)[0] == 1:
+            raise ValueError(f"evaluate_batch: --train-pool, but {exp_dir}'s config has no [MISC] seed_pool other than 1: "
+                             "its table was trained on the one scenario of its random_seed")
         groups.setdefault(_scenario_key(config), []).append((exp_dir, config))
     results = {}
     for members in groups.values():
@@ -140,6 +152,20 @@ def evaluate_batch(exp_dirs, n_envs, model_file="distr_q_model.pkl", seed0=None,
                     traffic = [ev.traffic(p) for p in range(P)]
         finally:
             ev.close()
+        if train_pool:  # the same tables on their own training scenarios
+            pseeds = [[runtime.episode_seed(int(cfg["MISC"]["random_seed"]), k) for k in range(n_envs)]
+                      for _, cfg in members]
+            ev = runtime.EvalBatch(env.compiled, hp, [s for ss in pseeds for s in ss], P, lib=lib, device=env.device,
+                                   max_steps=env.max_steps, malfunction_stream=env.malfunction_stream,
+                                   delay_threshold=env.delay_threshold)
+            try:
+                for p, (exp_dir, _) in enumerate(members):
+                    with open(os.path.join(exp_dir, model_file), "rb") as f:
+                        obj = pickle.load(f)
+                    ev.load_policy_dict(p, obj[0] if isinstance(obj, list) else obj)
+                pout = ev.evaluate([p for p in range(P) for _ in range(n_envs)])
+            finally:
+                ev.close()
         for p, (exp_dir, _) in enumerate(members):
             sel = slice(p * n_envs, (p + 1) * n_envs)
             out_dir = os.path.join(exp_dir, "eval_batch")
@@ -158,6 +184,19 @@ def evaluate_batch(exp_dirs, n_envs, model_file="distr_q_model.pkl", seed0=None,
             with open(os.path.join(out_dir, "summary.json"), "w") as f:
                 json.dump(summary, f, indent=1)
             results[exp_dir] = summary
+            if train_pool:
+                pcell = {k: (float(v[p]) if v.dtype.kind == "f" else int(v[p])) for k, v in pout["table"].items()}
+                pool_n = seed_schedule(members[p][1])[0]
+                tp = dict(exp_dir=exp_dir, model_file=model_file, policy=p, n_envs=n_envs, seed_pool=pool_n,
+                          seeds=[int(s) for s in pseeds[p]], n_trains=int(env.compiled.T), cell=pcell)
+                with open(os.path.join(out_dir, "train_pool.json"), "w") as f:
+                    json.dump(tp, f, indent=1)
+                np.savez_compressed(os.path.join(out_dir, "per_env_train_pool.npz"), seeds=np.array(pseeds[p], np.uint64),
+                                    cum_reward=pout["cum_reward"][sel], arrived=pout["arrived"][sel],
+                                    num_malfunctions=pout["num_malfunctions"][sel], decisions=pout["decisions"][sel],
+                                    ticks=pout["ticks"][sel], truncated=pout["truncated"][sel],
+                                    delays=pout["delays"][:, sel].T.astype(np.float64), at_dest=pout["at_dest"][:, sel].T)
+                summary["train_pool"] = tp
             if diagnose:
                 top = [int(i) for i in np.argsort(-hot[p].ravel().astype(np.int64), kind="stable")[:10] if hot[p].ravel()[i] > 0]
                 W = hot[p].shape[1]
@@ -195,11 +234,14 @@ if __name__ == "__main__":
     ap.add_argument("--record", type=int, default=0, metavar="K",
                     help="with --batch: record up to K episodes per experiment on the device (eval_batch/episode_<seed>.npz, "
                          "traffic.npz); with --diagnose those of envs with a stalled train")
+    ap.add_argument("--train-pool", action="store_true",
+                    help="with --batch: also score each table on the N seeds of its own training pool "
+                         "(eval_batch/train_pool.json); the config's [MISC] seed_pool must not be 1")
     ap.add_argument("--frames", action="store_true",
                     help="with --record: render every recorded decision (eval_batch/frames_<seed>/iter_<n>.png)")
     args = ap.parse_args()
     if args.batch > 0:
         evaluate_batch(args.exp_dirs, args.batch, args.model, args.seed0, diagnose=args.diagnose, stall=args.stall,
-                       record=args.record, frames=args.frames)
+                       record=args.record, frames=args.frames, train_pool=args.train_pool)
     else:
         evaluate(args.exp_dirs, args.model)

@@ -36,7 +36,7 @@ def grid_cells(hyperparams):
 
 
 def write_config(path, seed, exp_dir, checkpoint_freq, exploit_freq, env, gamma, default_q, params, num_episodes,
-                 n_envs=1, device=0):
+                 n_envs=1, device=0, seed_pool=1, heldout_exploit=False):
     config = configparser.ConfigParser()
     config["MISC"] = {"random_seed": seed, "out_dir": exp_dir, "checkpoint_freq": checkpoint_freq,
                       "exploit_freq": exploit_freq}
@@ -44,6 +44,10 @@ def write_config(path, seed, exp_dir, checkpoint_freq, exploit_freq, env, gamma,
         config["MISC"]["n_envs"] = str(n_envs)
     if device:
         config["MISC"]["device"] = str(device)
+    if int(seed_pool) != 1:
+        config["MISC"]["seed_pool"] = str(int(seed_pool))
+    if heldout_exploit:
+        config["MISC"]["heldout_exploit"] = "true"
     config["ENV"] = {k: str(v) for k, v in env.items()}
     config["MODEL"] = {"gamma": gamma, "epsilon": params["epsilon"], "epsilon_decay_rate": params["epsilon_decay_rate"],
                        "lr": params["lr"], "lr_decay_rate": params["lr_decay_rate"], "default_q": default_q,
@@ -54,11 +58,13 @@ def write_config(path, seed, exp_dir, checkpoint_freq, exploit_freq, env, gamma,
 
 
 def launch_sweep(random_seeds, out_dir, hyperparams, num_episodes, checkpoint_freq, exploit_freq, env, gamma=1.0,
-                 default_q=0.0, n_envs=1, device=0, lib=None):
+                 default_q=0.0, n_envs=1, device=0, lib=None, seed_pool=1, heldout_exploit=False):
     """Run the grid ``hyperparams`` (dict of lists, ``GRID_KEYS``) for every seed of ``random_seeds``.
 
     ``env``: the [ENV] section's keys (main.py: the size keys and malfunction settings, or ``scenario``).
     ``lib``: the library to run on (default: the HIP product library; tests pass the host build).
+    ``seed_pool`` / ``heldout_exploit``: main.py's optional [MISC] keys (the seed schedule), written into every
+    experiment's config.ini when they are not the defaults and passed to the batch.
     Returns the experiment directories, ``[idx][rdx]``."""
     ASyncSwitchEnv = importlib.import_module(PKG + ".env").ASyncSwitchEnv
     DistrQLearning = importlib.import_module(PKG + ".distr_q").DistrQLearning
@@ -72,7 +78,8 @@ def launch_sweep(random_seeds, out_dir, hyperparams, num_episodes, checkpoint_fr
         for idx, params in enumerate(cells):
             os.makedirs(dirs[idx][rdx], exist_ok=True)
             config = write_config(os.path.join(dirs[idx][rdx], "config.ini"), seed, dirs[idx][rdx], checkpoint_freq,
-                                  exploit_freq, env, gamma, default_q, params, num_episodes, n_envs, device)
+                                  exploit_freq, env, gamma, default_q, params, num_episodes, n_envs, device, seed_pool,
+                                  heldout_exploit)
         # one batch: env idx * n_envs + r is replica r of cell idx (group idx, seed + r)
         senv = ASyncSwitchEnv(main_mod.build_scenario(config), render_mode="human", max_steps=100_000,
                               n_envs=len(cells) * n_envs, device=int(device),
@@ -83,7 +90,8 @@ def launch_sweep(random_seeds, out_dir, hyperparams, num_episodes, checkpoint_fr
                                **{k: float(cells[0][k]) for k in GRID_KEYS},
                                seeds=[int(seed) + r for _ in cells for r in range(n_envs)],
                                hparam_groups=[{k: float(c[k]) for k in GRID_KEYS} for c in cells],
-                               env_group=[idx for idx in range(len(cells)) for _ in range(n_envs)], outputs=outputs)
+                               env_group=[idx for idx in range(len(cells)) for _ in range(n_envs)], outputs=outputs,
+                               seed_pool=int(seed_pool), heldout_exploit=bool(heldout_exploit))
         model.learn(num_episodes=int(num_episodes), out_dir=out_dir, checkpoint_freq=int(checkpoint_freq),
                     exploit_freq=int(exploit_freq))
         for sub, envs in outputs:

@@ -403,6 +403,46 @@ typedef struct {
 int sfl_set_hparam_groups(sfl_handle* h, int32_t n_groups, const sfl_hparam_group* groups,
                           const uint16_t* env_group /* [n_envs] */);
 
+/* ---- seed schedules: a fresh malfunction stream for every episode ----
+ * An env's seed keys its malfunction stream (the counter-based draw, oracle/flatland_lite.py mf_draw), and the
+ * reference resets every episode with the same one (env.reset(seed=self.seed)): every learning episode, exploit round
+ * and test() of an env replays one malfunction realisation.  A seed schedule derives each episode's seed from the
+ * env's create-time seed b_e (after sfl_state_restore: the record's) and the episode's index.  THE RULE -- the host
+ * build, the kernels, the Python layer and the tests implement it exactly:
+ *   sfl_episode_seed(base, k) = base                                                              for k == 0,
+ *                             = mix64(base * 0x9E3779B97F4A7C15 + k * 0xD1B54A32D192ED03 + 0x5EED5C4ED01E5EED)  otherwise
+ *     (mod 2^64; mix64 as in csrc/sfl_rng.h and oracle/flatland_lite.py).
+ *   pool == 1, flags == 0 is the default: every episode runs on b_e, as on a handle that never made the call.
+ *   A learning episode with index t -- the env's learning-episode index since sfl_learn_begin, the index curves bin
+ *     by -- runs on sfl_episode_seed(b_e, t % pool); with pool == 0 on sfl_episode_seed(b_e, t): no wrap, every
+ *     episode new.  Episode 0 always runs on b_e.
+ *   A greedy episode -- an exploit round of sfl_learn / sfl_step, or an episode of sfl_test -- runs on b_e (pool index
+ *     0, a training scenario), or with SFL_SEED_HELDOUT_EXPLOIT on sfl_episode_seed(b_e, SFL_SEED_HELD_OUT_EPISODE),
+ *     which no learning episode uses.  A greedy round does not advance t.
+ *   External-action mode: t counts the episodes the env has started since sfl_env_begin / sfl_env_begin_wave, minus
+ *     one; an SFL_ACTION_RESET starts a new episode like an episode end does.  No episode is greedy: the flag is refused
+ *     in this mode, and so are the begin calls on a handle that has it.  (A first call made after the begin counts
+ *     from the call: an env standing at its reset starts episode 0, any other env's episode in flight is episode 0.)
+ *   The seed holds for the whole episode: a launch whose decision budget ends inside an episode, or inside an exploit
+ *     round, resumes on the same seed.  A call takes effect at each env's next reset.  sfl_learn_begin restarts t at 0.
+ *   sfl_get_episode_seeds: per env the seed of the episode it started last (b_e before its first reset).
+ *   sfl_state_capture / sfl_state_restore continue bit for bit: the record of a handle that has left the default
+ *     carries, behind the fields of every record (the base seed among them), the running episode's seed, and its
+ *     fingerprint says so: such records restore into such handles only.  Restore into a handle with the schedule the
+ *     record was captured under (runtime.Batch.restore checks it).  Other handles' records and fingerprints are as before.
+ * A handle that has left the default launches kernels of its own (also after a return to the default, which they run
+ * by the rule); on it a per-decision trace (sfl_run_args.trace) is refused and the phase cycles do not advance, as on
+ * a handle with hyperparameter groups.  Refused, with a message and nothing changed: a graph-partitioned handle (and
+ * sfl_part_config on a scheduled one); an evaluation handle, whose seeds are chosen at create (derive them with
+ * sfl_episode_seed); a handle with a Flatland malfunction table (sfl_set_mf_schedule with steps > 0, and that call on
+ * a scheduled handle); pool > 2^31 - 1; unknown flag bits. */
+#define SFL_SEED_HELD_OUT_EPISODE 0xFFFFFFFFFFFFFFFFull
+#define SFL_SEED_HELDOUT_EXPLOIT  1u
+uint64_t sfl_episode_seed(uint64_t base, uint64_t k);
+int sfl_set_seed_schedule(sfl_handle* h, uint32_t pool, uint32_t flags);
+int sfl_get_seed_schedule(sfl_handle* h, uint32_t* pool, uint32_t* flags);
+int sfl_get_episode_seeds(sfl_handle* h, uint64_t* out /* [n_envs] */);
+
 /* ---- consensus Q-tables: a cohort's learners merged on the device, and shared ----
  * The envs of a handle are independent learners.  sfl_consensus merges their Q-tables per cohort -- env e belongs
  * to cohort env_cohort[e] (SFL_NO_COHORT: to none; it is neither read nor written) -- into one consensus table and

@@ -1,7 +1,11 @@
 """Launch a training run from an ini file (the reference's main.py -c config.ini).
 
 Sections/keys as in the reference (main.py:21-60; writer hyperparam_tuning.py:49-82):
-  [MISC]  random_seed, out_dir, checkpoint_freq, exploit_freq   (+ optional n_envs, device)
+  [MISC]  random_seed, out_dir, checkpoint_freq, exploit_freq   (+ optional n_envs, device; optional seed_pool
+          and heldout_exploit, the seed schedule of runtime.Batch.set_seed_schedule: learning episode t runs on
+          runtime.episode_seed(random_seed, t % seed_pool) -- 0: a new scenario every episode -- and with
+          heldout_exploit = true the exploit rounds run on a held-out seed.  Absent: every episode replays the
+          malfunctions of random_seed, as in the reference)
   [ENV]   width, height, max_num_cities, max_rails_between_cities, max_rail_pairs_in_city,
           number_of_agents, malfunction_rate, min_duration, max_duration   (+ optional scenario:
           a mapgen config name or a scenario JSON path, used instead of the size keys; optional
@@ -40,6 +44,12 @@ def build_scenario(config):
                                        int(env["number_of_agents"]), seed, malfunction=mf, **opt)
 
 
+def seed_schedule(config):
+    """(seed_pool, heldout_exploit) of a config's [MISC] section; (1, False) where the keys are absent."""
+    misc = config["MISC"]
+    return int(misc.get("seed_pool", 1)), misc.getboolean("heldout_exploit", fallback=False)
+
+
 def launch_experiment(config_path, lib=None):
     """``lib``: the library handle to run on (default: the HIP product library; tests pass the host build)."""
     start_time = time.time()
@@ -54,10 +64,12 @@ def launch_experiment(config_path, lib=None):
     env = ASyncSwitchEnv(build_scenario(config), render_mode="human", max_steps=100_000, n_envs=n_envs, device=device,
                          malfunction_stream=config["ENV"].get("malfunction_stream", "counter"))
     m = config["MODEL"]
+    seed_pool, heldout_exploit = seed_schedule(config)
     model = DistrQLearning(env=env, gamma=float(m["gamma"]), epsilon=float(m["epsilon"]),
                            epsilon_decay_rate=float(m["epsilon_decay_rate"]), lr=float(m["lr"]),
                            lr_decay_rate=float(m["lr_decay_rate"]), default_q=float(m["default_q"]),
-                           seed=int(config["MISC"]["random_seed"]), lib=lib)
+                           seed=int(config["MISC"]["random_seed"]), lib=lib, seed_pool=seed_pool,
+                           heldout_exploit=heldout_exploit)
     n_ep = int(m["num_episodes"])
     model.learn(num_episodes=n_ep, out_dir=out_dir, checkpoint_freq=checkpoint_freq, exploit_freq=exploit_freq)
     model.save(os.path.join(out_dir, "distr_q_model.pkl"))

@@ -208,6 +208,11 @@ EXPORTS = {
     "sfl_part_get_q": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_double), P(C.c_uint32)]),
     # hyperparameter groups (runtime.Batch hparam_groups, sweep.py)
     "sfl_set_hparam_groups": (C.c_int, [C.c_void_p, C.c_int32, P(HParamGroup), P(C.c_uint16)]),
+    # seed schedules (runtime.Batch seed_pool / set_seed_schedule / episode_seeds); sfl_episode_seed, the one entry
+    # point that returns a uint64_t, is bound beside this table (Lib.__init__)
+    "sfl_set_seed_schedule": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "sfl_get_seed_schedule": (C.c_int, [C.c_void_p, P(C.c_uint32), P(C.c_uint32)]),
+    "sfl_get_episode_seeds": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
     # consensus Q-tables (runtime.Batch consensus / consensus_raw)
     "sfl_consensus": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_double)]),
     "sfl_get_consensus_q": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_double), P(C.c_uint32)]),
@@ -251,6 +256,10 @@ EXPORTS = {
 }
 
 
+SEED_HELD_OUT_EPISODE = 0xFFFFFFFFFFFFFFFF  # SFL_SEED_HELD_OUT_EPISODE
+SEED_HELDOUT_EXPLOIT = 1                    # SFL_SEED_HELDOUT_EXPLOIT
+
+
 class SflError(RuntimeError):
     pass
 
@@ -265,6 +274,8 @@ class Lib:
             fn = getattr(self.dll, name)
             fn.restype = res
             fn.argtypes = args
+        self.dll.sfl_episode_seed.restype = C.c_uint64
+        self.dll.sfl_episode_seed.argtypes = [C.c_uint64, C.c_uint64]
         if self.dll.sfl_abi_version() != ABI_VERSION:
             raise SflError("ABI version mismatch")
         self.build_id = self.dll.sfl_build_id().decode()

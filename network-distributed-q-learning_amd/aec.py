@@ -47,6 +47,11 @@ class AECBatch:
     or None: ``os.environ.get("SFL_ENV_KERNEL", "lane")``, read at creation like ``SFL_KERNEL`` and ``SFL_WAVE_G``.
     Both give the same outputs bit for bit.  ``"wave"`` raises ``SflError`` with the library's reason where it cannot
     be honoured (a map without a wave shape, ``SFL_KERNEL=scalar``, the host build); any other value ``ValueError``.
+
+    ``seed_pool``: the seed schedule (``Batch.set_seed_schedule``): the n-th episode an env starts (n = 0, 1, ...; an
+    ``ACTION_RESET`` starts one like an episode end does) runs on ``runtime.episode_seed(seeds[e], n % seed_pool)``, with
+    0 on ``episode_seed(seeds[e], n)``.  The default, 1, replays one malfunction realisation per env, as the reference.
+    ``batch.episode_seeds()`` reads the running episodes' seeds.
     """
 
     KERNELS = ("lane", "wave")
@@ -56,7 +61,7 @@ class AECBatch:
 
     def __init__(self, cm: CompiledMap, seeds: Sequence[int], lib: Optional[_lib.Lib] = None, device: int = 0,
                  max_steps: int = 100_000, malfunction_stream: str = "counter", delay_threshold: int = 20,
-                 kernel: Optional[str] = None):
+                 kernel: Optional[str] = None, seed_pool: int = 1):
         if kernel is None:
             kernel = os.environ.get("SFL_ENV_KERNEL", "lane")
         if kernel not in self.KERNELS:
@@ -64,7 +69,7 @@ class AECBatch:
         self.kernel = kernel
         self.cm = cm
         self.batch = Batch(cm, _ENV_HP, seeds, lib=lib, device=device, max_steps=max_steps, ntab=16,
-                           malfunction_stream=malfunction_stream, delay_threshold=delay_threshold)
+                           malfunction_stream=malfunction_stream, delay_threshold=delay_threshold, seed_pool=seed_pool)
         self.lib = self.batch.lib
         self.E = self.batch.E
         E, T = self.E, cm.T

@@ -22,7 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("SFL_ARCH", "gfx950")
-SOURCES = ["sfl.hip", "sfl_kwave_v7.hip", "sfl_kwave_hpg.hip", "sfl_kwave_hpg_v7.hip", "sfl_kwave_ext.hip", "sfl_kwave_bank.hip", "sfl_consensus.hip", "sfl_consensus.h", "sfl_cells.h", "sfl_launch.h", "sfl_curve.hip", "sfl_curve.h", "sfl_eval.hip", "sfl_eval.h", "sfl_diag.hip", "sfl_diag.h", "sfl_rec.hip", "sfl_rec.h", "sfl_snap.hip", "sfl_snap.h", "sfl_trans.hip", "sfl_trans.h", "sfl_kwave_g.h", "sfl_core.h", "sfl_wave.h", "sfl_rng.h", "sfl_engine.h", "sfl_part.h",
+SOURCES = ["sfl.hip", "sfl_kwave_v7.hip", "sfl_kwave_hpg.hip", "sfl_kwave_hpg_v7.hip", "sfl_kwave_ext.hip", "sfl_kwave_bank.hip", "sfl_kwave_sched.hip", "sfl_kwave_sched_hpg.hip", "sfl_kwave_sched_v7.hip", "sfl_kwave_sched_ext.hip", "sfl_consensus.hip", "sfl_consensus.h", "sfl_cells.h", "sfl_launch.h", "sfl_curve.hip", "sfl_curve.h", "sfl_eval.hip", "sfl_eval.h", "sfl_diag.hip", "sfl_diag.h", "sfl_rec.hip", "sfl_rec.h", "sfl_snap.hip", "sfl_snap.h", "sfl_trans.hip", "sfl_trans.h", "sfl_kwave_g.h", "sfl_core.h", "sfl_wave.h", "sfl_rng.h", "sfl_engine.h", "sfl_part.h",
            "sfl_mfgen.h", "sfl_capi.inc", "sfl_hostsim.cpp", "sfl_experiment.h", os.path.join("..", "..", "include", "sfl.h")]
 # libsfl.so's translation units and the compiler flags each adds to the common ones: variant 7 of k_wave_g (the
 # bench's c3 shape) with LLVM's register-minimising machine scheduler -- c3 +6.5 %, every other kernel loses with
@@ -31,12 +31,14 @@ SOURCES = ["sfl.hip", "sfl_kwave_v7.hip", "sfl_kwave_hpg.hip", "sfl_kwave_hpg_v7
 # scheduler; external-action mode's wave kernels (sfl_env_begin_wave) likewise a unit of their own, and so are the
 # consensus kernels (sfl_consensus), the learning-curve fold (sfl_curve), the policy-bank evaluation's wave kernels
 # (sfl_kwave_bank) its fold (sfl_eval), its non-arrival diagnosis (sfl_diag) and its recordings' traffic fold (sfl_rec), the suspend / resume passes (sfl_snap) and external-action mode's transition
-# assembler (sfl_trans).  Part of the build id
+# assembler (sfl_trans).  The kernels of handles with a seed schedule (sfl_set_seed_schedule) are four more units: the
+# plain, the grouped and the external-action launches, and variant 7's with variant 7's scheduler.  Part of the build id
 # (kernel_source_sha1).
 _V7_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]
 TUS = {"sfl.hip": [], "sfl_kwave_v7.hip": _V7_FLAGS, "sfl_kwave_hpg.hip": [], "sfl_kwave_hpg_v7.hip": _V7_FLAGS,
        "sfl_kwave_ext.hip": [], "sfl_kwave_bank.hip": [], "sfl_consensus.hip": [], "sfl_curve.hip": [], "sfl_eval.hip": [], "sfl_diag.hip": [], "sfl_rec.hip": [], "sfl_snap.hip": [],
-       "sfl_trans.hip": []}
+       "sfl_trans.hip": [], "sfl_kwave_sched.hip": [], "sfl_kwave_sched_hpg.hip": [], "sfl_kwave_sched_v7.hip": _V7_FLAGS,
+       "sfl_kwave_sched_ext.hip": []}
 _MARK = re.compile(rb"SFL_BUILD_ID:([0-9a-f]{40})")
 _DEFS = re.compile(rb"SFL_BUILD_DEFS:\[([^\]\x00]*)\]")
 _FLAGS = re.compile(rb"SFL_BUILD_FLAGS:\[([^\]\x00]*)\]")

@@ -736,9 +736,12 @@ struct HipBackend {
     const bool hpg = m.env_group != nullptr;
     // policy-bank evaluation (sfl_bank_eval): the BANK instantiation; k_run reads the map's bank pointer at run time
     const bool bank = c.mode == sfl::MODE_BANK;
+    // a seed schedule (sfl_set_seed_schedule): the SCHED instantiations, plain and HPG (the engine refuses a trace and
+    // passes no phase counters); k_run reads the map's schedule at run time
+    const bool sched = m.seed_sched != 0 && !bank;
     if (variant >= 1 && variant < sfl::kNumVariants)
       sflk::launch({variant,
-                    bank ? (c.rec_slot ? sflk::Mode::BankRec : sflk::Mode::Bank) : hpg ? sflk::Mode::Hpg : c.trace ? sflk::Mode::Trace : c.phase_cyc ? sflk::Mode::Timed : sflk::Mode::Plain,
+                    sched ? (hpg ? sflk::Mode::SchedHpg : sflk::Mode::Sched) : bank ? (c.rec_slot ? sflk::Mode::BankRec : sflk::Mode::Bank) : hpg ? sflk::Mode::Hpg : c.trace ? sflk::Mode::Trace : c.phase_cyc ? sflk::Mode::Timed : sflk::Mode::Plain,
                     s.E, stream, pm, ps, pc});
     else sfl::with_nw(m.T, [&](auto nw) { k_run<decltype(nw)::value><<<blocks, 256, 0, stream>>>(pm, ps, pc); });
     if (!check(hipGetLastError(), "k_run launch")) return -1;
@@ -748,7 +751,8 @@ struct HipBackend {
   void launch_ext(int variant, const sfl::SflMap& m, uint32_t E, const sfl::SflMap* pm, const sfl::SflState* ps,
                   const sfl::SflCtl* pc) {
     const unsigned blocks = (E + 63) / 64;  // (64-thread blocks: few envs, spread over the CUs)
-    if (variant >= 1 && variant < sfl::kNumVariants) sflk::launch({variant, sflk::Mode::Ext, E, stream, pm, ps, pc});
+    if (variant >= 1 && variant < sfl::kNumVariants)
+      sflk::launch({variant, m.seed_sched != 0 ? sflk::Mode::SchedExt : sflk::Mode::Ext, E, stream, pm, ps, pc});
     else sfl::with_nw(m.T, [&](auto nw) { k_run_ext<decltype(nw)::value><<<blocks, 64, 0, stream>>>(pm, ps, pc); });
   }
   // external-action mode: one call = every env applies its action and runs to its next observation

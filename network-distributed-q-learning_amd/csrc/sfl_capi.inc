@@ -330,6 +330,23 @@ int sfl_set_hparam_groups(sfl_handle* h, int32_t n_groups, const sfl_hparam_grou
   return sfl::set_hparam_groups(HH(h), n_groups, groups, env_group);
 }
 
+uint64_t sfl_episode_seed(uint64_t base, uint64_t k) { return sfl::episode_seed(base, k); }
+
+int sfl_set_seed_schedule(sfl_handle* h, uint32_t pool, uint32_t flags) {
+  if (!h) return sfl::fail("sfl_set_seed_schedule: null handle");
+  return sfl::set_seed_schedule(HH(h), pool, flags);
+}
+
+int sfl_get_seed_schedule(sfl_handle* h, uint32_t* pool, uint32_t* flags) {
+  if (!h) return sfl::fail("sfl_get_seed_schedule: null handle");
+  return sfl::get_seed_schedule(HH(h), pool, flags);
+}
+
+int sfl_get_episode_seeds(sfl_handle* h, uint64_t* out) {
+  if (!h) return sfl::fail("sfl_get_episode_seeds: null handle");
+  return sfl::get_episode_seeds(HH(h), out);
+}
+
 int sfl_consensus(sfl_handle* h, int32_t mode, uint32_t flags, uint32_t n_cohorts, const uint32_t* env_cohort,
                   double* kernel_ms) {
   if (!h) return sfl::fail("sfl_consensus: null handle");

@@ -148,6 +148,12 @@ struct SflMap {
   // has no per-env table or key set (SflState::q and touched are null), and a greedy run inserts no key-set row.
   const double* bank_q;
   const uint32_t* bank_policy;  // [E], the table each env follows in the current sfl_bank_eval
+  // seed schedule (sfl_set_seed_schedule).  seed_sched == 0: every episode on the env's base seed,
+  // SflState::seed, and nothing below is read.  Otherwise an episode's seed is sched_seed(base, seed_pool, seed_flags,
+  // episode index, greedy), derived at its reset and held in SflState::ep_seed between launches.  (Last in the
+  // struct: the kernels of unscheduled handles read the same offsets as before.)
+  int32_t seed_sched;
+  uint32_t seed_pool, seed_flags;
 };
 static_assert(offsetof(SflMap, dec) == 0 && offsetof(SflMap, lrn) == 32 && offsetof(SflMap, upd) == 64,
               "decide() reads bytes 0-63 of the map, post() bytes 32-95");
@@ -236,6 +242,9 @@ struct SflState {
   uint8_t* claim;       // [H*W][E] motion-check claim or 0xFF
   uint64_t* sem;        // [NP][E] semaphore records
   StateLearn lrn;
+  // seed schedule: [E] the seed of the episode each env started last (the base seed until a scheduled launch);
+  // read at a scheduled launch's start and written at its end, never by an unscheduled one
+  uint64_t* ep_seed;
 };
 static_assert(offsetof(SflState, lrn) % 32 == 0, "the learner's pointers: one aligned 32-byte run");
 
@@ -431,11 +440,12 @@ struct Env {
   int32_t now;      // rail_env._elapsed_steps
   uint32_t flags;
   uint32_t epoch;
+  uint64_t seed;    // the running episode's seed: the env's base seed, or the seed schedule's (env_run / env_run_ext)
   // train bitmasks kept in registers for the whole launch: 0 decision queue, 1 arrived,
   // 2 destination bonus paid, 3 in malfunction at the previous tick
   uint32_t msk[4][NW];
 
-  SFL_FN Env(const SflMap& m_, const SflState& s_, uint32_t e_) : m(m_), s(s_), e(e_), E(s_.E), err(0), now(0), flags(0), epoch(0) {
+  SFL_FN Env(const SflMap& m_, const SflState& s_, uint32_t e_) : m(m_), s(s_), e(e_), E(s_.E), err(0), now(0), flags(0), epoch(0), seed(s_.seed[e_]) {
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -761,7 +771,7 @@ SFL_FN void env_tick(V& v, int32_t* last_move = nullptr) {
   const SflMap& m = v.m;
   const SflState& s = v.s;
   const int32_t t = ++v.now;
-  const uint64_t seed = s.seed[v.e];
+  const uint64_t seed = v.seed;
   constexpr int NW = V::kNW;
   uint32_t movers[NW] = {};
 
@@ -1367,6 +1377,10 @@ SFL_FN void env_run(const SflMap& m, const SflState& s, const SflCtl& c, uint32_
   v.now = s.elapsed[e];
   v.epoch = s.epoch[e];
   v.err = s.err[e];
+  // seed schedule: the running episode's seed as the last launch left it; a reset derives the next one
+  const bool sched = m.seed_sched != 0 && c.mode != MODE_BANK;
+  const uint64_t seed_base = v.seed;
+  if (sched) v.seed = s.ep_seed[e];
   int32_t phase = s.phase[e];
   uint64_t dec = 0, ticks = 0, abytes = 0;
   Decision d;
@@ -1392,6 +1406,7 @@ SFL_FN void env_run(const SflMap& m, const SflState& s, const SflCtl& c, uint32_
         if (c.exploit_freq > 0 && (t + 1) % c.exploit_freq == 0 && !(v.flags & F_EXPLOIT_DONE)) v.flags |= F_GREEDY;
         else v.flags &= ~F_GREEDY;
       }
+      if (sched) v.seed = sched_seed(seed_base, m.seed_pool, m.seed_flags, s.ep_t[e], (v.flags & F_GREEDY) != 0);
       env_reset(v);
       // (the bank episode's record of the trains' last moves is kept in its output buffer: the launch is that one episode)
       if (last_move)
@@ -1511,6 +1526,7 @@ SFL_FN void env_run(const SflMap& m, const SflState& s, const SflCtl& c, uint32_
   s.epoch[e] = v.epoch;
   s.err[e] = v.err;
   s.cum_reward[e] = cum;
+  if (sched) s.ep_seed[e] = v.seed;
   if (c.launch_dec) c.launch_dec[e] = dec;
   if (c.launch_ticks) c.launch_ticks[e] = ticks;
   if (c.launch_bytes) c.launch_bytes[e] = abytes;
@@ -1531,6 +1547,10 @@ SFL_FN void env_run_ext(const SflMap& m, const SflState& s, const SflCtl& c, uin
   v.now = s.elapsed[e];
   v.epoch = s.epoch[e];
   v.err = s.err[e];
+  // seed schedule: ep_t counts the episodes the env has started since sfl_env_begin, minus one; no episode is greedy
+  const bool sched = m.seed_sched != 0;
+  const uint64_t seed_base = v.seed;
+  if (sched) v.seed = s.ep_seed[e];
   int32_t phase = s.phase[e];
   uint64_t ticks = 0;
   Decision d;
@@ -1549,6 +1569,11 @@ SFL_FN void env_run_ext(const SflMap& m, const SflState& s, const SflCtl& c, uin
   }
   while (true) {
     if (phase == PH_RESET) {
+      if (sched) {
+        const int32_t t = s.ep_t[e] + 1;
+        s.ep_t[e] = t;
+        v.seed = sched_seed(seed_base, m.seed_pool, m.seed_flags, t, false);
+      }
       env_reset(v);
       phase = PH_TICK;
     } else if (phase == PH_TICK) {
@@ -1618,6 +1643,7 @@ SFL_FN void env_run_ext(const SflMap& m, const SflState& s, const SflCtl& c, uin
   s.eflags[e] = v.flags;
   s.epoch[e] = v.epoch;
   s.err[e] = v.err;
+  if (sched) s.ep_seed[e] = v.seed;
   if (c.launch_dec) c.launch_dec[e] = applied ? 1u : 0u;
   if (c.launch_ticks) c.launch_ticks[e] = ticks;
   if (c.launch_bytes) c.launch_bytes[e] = 0;

@@ -709,6 +709,8 @@ template <class B>
 int set_mf_schedule(Handle<B>* h, int32_t steps, const uint8_t* table) {
   SflMap& m = h->map;
   if (steps < 0 || (steps > 0 && !table)) return fail("sfl_set_mf_schedule: bad argument");
+  if (steps > 0 && m.seed_sched)
+    return fail("sfl_set_mf_schedule: the handle has a seed schedule (sfl_set_seed_schedule), which keys the counter-based draw");
   if (m.mf_tab) {
     h->dfree((void*)m.mf_tab);
     m.mf_tab = nullptr;
@@ -782,6 +784,66 @@ int set_hparam_groups(Handle<B>* h, int32_t n_groups, const sfl_hparam_group* gr
   return 0;
 }
 
+// Seed schedules (include/sfl.h sfl_set_seed_schedule).  The schedule lives in the map (seed_sched,
+// seed_pool, seed_flags); the seed of the episode each env started last in SflState::ep_seed, allocated by the first
+// call that leaves the default and filled with the base seeds -- the episodes in flight run on them to their end.
+// From then on the handle launches the scheduled kernels, also after a return to pool 1 / flags 0 (which they run as
+// the rule states it: every episode on the base seed), so that a call always takes effect at each env's next reset.
+// Everything is validated before anything changes.
+template <class B>
+int set_seed_schedule(Handle<B>* h, uint32_t pool, uint32_t flags) {
+  const std::string fn = "sfl_set_seed_schedule: ";
+  if (h->bank.on)
+    return fail(fn + "an evaluation handle's seeds are chosen at create (sfl_create_eval); derive them with sfl_episode_seed");
+  if (h->part.world) return fail(fn + "the handle is graph-partitioned");
+  if (h->map.mf_steps > 0)
+    return fail(fn + "the handle has a Flatland malfunction table (sfl_set_mf_schedule), which no seed keys");
+  if (pool > 0x7FFFFFFFu) return fail(fn + "pool " + std::to_string(pool) + " beyond 2^31 - 1");
+  if (flags & ~SEED_HELDOUT_EXPLOIT) return fail(fn + "unknown flag bits " + std::to_string(flags & ~SEED_HELDOUT_EXPLOIT));
+  if (h->env_mode && (flags & SEED_HELDOUT_EXPLOIT))
+    return fail(fn + "SFL_SEED_HELDOUT_EXPLOIT in external-action mode, where no episode is greedy");
+  SflMap& m = h->map;
+  if (!m.seed_sched && pool == 1 && flags == 0) return 0;  // the default on a handle that never left it
+  const size_t E = h->E;
+  if (!m.seed_sched) {
+    if (!h->st.ep_seed) h->st.ep_seed = h->template dalloc<uint64_t>(E);
+    if (!h->st.ep_seed) return fail(fn + "device allocation failed");
+    h->be.h2d(h->st.ep_seed, h->seeds.data(), E * 8);
+    if (h->env_mode) {
+      // external-action mode counts started episodes in ep_t from here: an env that stands at its reset starts
+      // episode 0 there, the episode in flight of any other is episode 0
+      std::vector<int32_t> ph(E), t(E);
+      h->be.d2h(ph.data(), h->st.phase, E * 4);
+      if (h->be.sync()) return fail(fn + h->be.error());
+      for (size_t e = 0; e < E; ++e) t[e] = ph[e] == PH_RESET ? -1 : 0;
+      h->be.h2d(h->st.ep_t, t.data(), E * 4);
+    }
+    if (h->be.sync()) return fail(fn + h->be.error());
+  }
+  m.seed_sched = 1;
+  m.seed_pool = pool;
+  m.seed_flags = flags;
+  return 0;
+}
+
+template <class B>
+int get_seed_schedule(Handle<B>* h, uint32_t* pool, uint32_t* flags) {
+  if (pool) *pool = h->map.seed_sched ? h->map.seed_pool : 1u;
+  if (flags) *flags = h->map.seed_sched ? h->map.seed_flags : 0u;
+  return 0;
+}
+
+template <class B>
+int get_episode_seeds(Handle<B>* h, uint64_t* out) {
+  if (!out) return fail("sfl_get_episode_seeds: null argument");
+  if (!h->map.seed_sched) {
+    memcpy(out, h->seeds.data(), (size_t)h->E * 8);
+    return 0;
+  }
+  h->be.d2h(out, h->st.ep_seed, (size_t)h->E * 8);
+  return h->be.sync() ? fail(std::string("sfl_get_episode_seeds: ") + h->be.error()) : 0;
+}
+
 template <class B>
 int part_host_access(Handle<B>* h, bool write);
 template <class B>
@@ -800,6 +862,7 @@ int learn_begin(Handle<B>* h, const uint64_t* rng_states) {
   h->be.h2d(h->st.rng, soa.data(), soa.size() * 8);
   h->be.memset(h->st.lrn.counts, 0, (size_t)h->map.lrn.S * E * 4);
   h->be.memset(h->st.ep_t, 0, E * 4);
+  if (h->map.seed_sched) h->be.h2d(h->st.ep_seed, h->seeds.data(), E * 8);  // (the base seed before the first reset)
   // every env starts the learn() call with a fresh reset, and no exploit round done yet
   std::vector<int32_t> ph(E, PH_RESET);
   h->be.h2d(h->st.phase, ph.data(), E * 4);
@@ -923,9 +986,11 @@ int run(Handle<B>* h, const SflCtl& c_in, sfl_run_args* args) {
   if (h->part.world) return fail("sfl_run: the handle is graph-partitioned; drive it with sfl_part_*");
   if (h->env_mode) return fail("sfl_run: the handle is in external-action mode (sfl_env_begin); drive it with sfl_env_step");
   // (the grouped kernels are built plain only: no traced and no phase-timed instantiation)
-  const bool grouped = h->map.env_group != nullptr;
+  // (nor the kernels of a handle with a seed schedule)
+  const bool grouped = h->map.env_group != nullptr || h->map.seed_sched != 0;
   if (grouped && args && args->trace && args->trace_cap > 0)
-    return fail("sfl_run: a per-decision trace is not available on a handle with hyperparameter groups");
+    return fail(h->map.env_group ? "sfl_run: a per-decision trace is not available on a handle with hyperparameter groups"
+                                 : "sfl_run: a per-decision trace is not available on a handle with a seed schedule");
   SflCtl c = c_in;
   const size_t E = h->E, T = h->map.T;
   const int32_t cap = args ? args->stats_cap : 0;
@@ -1548,6 +1613,8 @@ int env_begin(Handle<B>* h, bool wave = false) {
   if (h->bank.on) return fail(fn + ": an evaluation handle runs sfl_bank_eval only (sfl_create_eval)");
   if (h->part.world) return fail(fn + ": the handle is graph-partitioned");
   if (h->map.env_group) return fail(fn + ": the handle has hyperparameter groups (sfl_set_hparam_groups)");
+  if (h->map.seed_sched && (h->map.seed_flags & SEED_HELDOUT_EXPLOIT))
+    return fail(fn + ": the handle's seed schedule has SFL_SEED_HELDOUT_EXPLOIT, and no episode of this mode is greedy");
   int variant = 0;
   if (wave) {
     if (!B::kHasWave)
@@ -1606,6 +1673,11 @@ int env_begin(Handle<B>* h, bool wave = false) {
   h->be.memset(st.sem, 0, NP * E * 8);
   h->be.memset(st.lrn.slot, 0, S * T * E * 8);
   h->be.memset(st.step_ctr, 0, E * 8);
+  // a seed schedule counts the episodes an env has started since here, minus one, in ep_t
+  if (h->map.seed_sched) {
+    h->be.memset(st.ep_t, 0xFF, E * 4);
+    h->be.h2d(st.ep_seed, h->seeds.data(), E * 8);  // (the base seed before the first reset)
+  }
   std::vector<int32_t> none(E, -1);
   h->be.h2d((void*)h->ext.actions, none.data(), E * 4);
   return h->be.sync() ? fail(h->be.error()) : 0;
@@ -1741,6 +1813,7 @@ int part_config(Handle<B>* h, int rank, int world, const int32_t* owner, uint32_
   if (world < 1 || rank < 0 || rank >= world || world > 255) return fail("sfl_part_config: bad rank / world");
   if (h->part.world) return fail("sfl_part_config: already configured");
   if (h->map.env_group) return fail("sfl_part_config: the handle has hyperparameter groups (sfl_set_hparam_groups)");
+  if (h->map.seed_sched) return fail("sfl_part_config: the handle has a seed schedule (sfl_set_seed_schedule)");
   if (env_base + h->E > E_tot) return fail("sfl_part_config: env range outside envs_total");
   if (cap_req < h->E) return fail("sfl_part_config: request capacity must hold one request per local env");
   if (cap_upd < 1 || (uint64_t)cap_req + cap_upd >= (1ull << 31) || (uint64_t)world * (cap_req + cap_upd + 1ull) >= (1ull << 32))
@@ -2480,7 +2553,10 @@ uint32_t snap_fields(Handle<B>* h, SnapField* f, uint32_t* n_fields, uint32_t* s
   else add(s.sem, 8, NP, 0);
   add(s.lrn.slot, 8, S * T, wave);
   add(s.lrn.counts, 4, S, wave);
-  static_assert(SNAP_MAX_FIELDS >= 35, "fields");
+  // a handle with a seed schedule: the running episode's seed too (a call takes effect at the next reset only, so the
+  // value does not follow from the schedule and the episode index).  Other handles' records are what they were.
+  if (m.seed_sched) add(s.ep_seed, 8, 1, 0);
+  static_assert(SNAP_MAX_FIELDS >= 36, "fields");
   *n_fields = n;
   return (off + 7u) / 8u * 8u;
 }
@@ -2492,7 +2568,12 @@ uint64_t snap_fingerprint(Handle<B>* h) {
   fp = snap_hash(fp, &m.upd.gamma, 8);
   fp = snap_hash(fp, &m.dec.default_q, 8);
   const int64_t sc[] = {m.lrn.ntab, m.max_steps, m.dec.delay_thr, m.mf_steps > 0 ? 1 : 0, h->variant > 0 ? 1 : 0};
-  return snap_hash(fp, sc, sizeof sc);
+  fp = snap_hash(fp, sc, sizeof sc);
+  if (m.seed_sched) {  // (its records carry one more field; an unscheduled handle's fingerprint is what it was)
+    const int64_t sched = 1;
+    fp = snap_hash(fp, &sched, sizeof sched);
+  }
+  return fp;
 }
 
 template <class B>

@@ -90,6 +90,24 @@ k_wave_g_bank_rec(const sfl::SflMap* __restrict__ m, const sfl::SflState* __rest
   sfl::wave::run_groups<PPL, SPL, TW, false, G, false, LM, false, false, true, true>(*m, *s, *c);
 }
 
+// SCHED: handles with a seed schedule (sfl_set_seed_schedule; sfl_wave.h SCHED): the plain, the HPG and the EXT launch
+// of every shape, again as kernels of their own names, so that every other handle runs the kernels it ran before
+template <int PPL, int SPL, int TW, bool HPG, bool EXT>
+__global__ void __launch_bounds__(SFL_WAVE_BLOCK) __attribute__((amdgpu_waves_per_eu(SFL_WAVE_OCC)))
+k_wave_sched(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict__ s, const sfl::SflCtl* __restrict__ c) {
+  sfl::wave::run<PPL, SPL, TW, false, false, false, HPG, EXT, false, false, true>(*m, *s, *c);
+}
+template <int PPL, int SPL, int TW, bool HPG, bool EXT>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SFL_WAVE2_OCC)))
+k_wave2_sched(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict__ s, const sfl::SflCtl* __restrict__ c) {
+  sfl::wave::run<PPL, SPL, TW, false, false, false, HPG, EXT, false, false, true>(*m, *s, *c);
+}
+template <int PPL, int SPL, int TW, int G, int OCC, bool LM, bool HPG, bool EXT>
+__global__ void __launch_bounds__(SFL_GROUP_BLOCK) __attribute__((amdgpu_waves_per_eu(OCC)))
+k_wave_g_sched(const sfl::SflMap* __restrict__ m, const sfl::SflState* __restrict__ s, const sfl::SflCtl* __restrict__ c) {
+  sfl::wave::run_groups<PPL, SPL, TW, false, G, false, LM, HPG, EXT, false, false, true>(*m, *s, *c);
+}
+
 // ---- one launch path from the shape table ---------------------------------------------------------------------
 // A cell = a row v of sfl::kVariants (1 .. kNumVariants - 1) x a launch mode.  Everything about a cell follows from
 // the row: its kernel family, its grid and block, and the translation unit that compiles it.
@@ -100,15 +118,20 @@ static_assert(sizeof(sfl::kVariants) / sizeof(sfl::kVariants[0]) == sfl::kNumVar
 // launch is a whole episode, hundreds of decisions per env, which is what the copy of the tables into LDS pays for;
 // external-action mode's single decision per launch is not)
 // BankRec: the same launch with a recording armed (sfl_bank_record): every row again
-enum class Mode { Plain, Trace, Timed, Hpg, Ext, Bank, BankRec };
+// Sched / SchedHpg / SchedExt: Plain / Hpg / Ext on a handle with a seed schedule (sfl_set_seed_schedule)
+enum class Mode { Plain, Trace, Timed, Hpg, Ext, Bank, BankRec, Sched, SchedHpg, SchedExt };
 // libsfl.so's translation units (build.TUS): sfl.hip, sfl_kwave_v7.hip, sfl_kwave_hpg.hip, sfl_kwave_hpg_v7.hip,
-// sfl_kwave_ext.hip, sfl_kwave_bank.hip
-enum class Unit { Main, V7, Hpg, HpgV7, Ext, Bank };
+// sfl_kwave_ext.hip, sfl_kwave_bank.hip, sfl_kwave_sched.hip, sfl_kwave_sched_hpg.hip, sfl_kwave_sched_v7.hip,
+// sfl_kwave_sched_ext.hip
+enum class Unit { Main, V7, Hpg, HpgV7, Ext, Bank, Sched, SchedHpg, SchedV7, SchedExt };
 constexpr int kSchedVariant = 7;  // the bench's c3 shape: its units are built with the register-minimising scheduler
 // the unit that owns a cell: it alone instantiates the cell's kernel, with its own compiler flags.  Every cell has
 // exactly one owner (this function's value); a unit that does not define its launch_unit fails the link.
 constexpr Unit owner(int v, Mode md) {
   if (md == Mode::Ext) return Unit::Ext;
+  if (md == Mode::SchedExt) return Unit::SchedExt;
+  if (md == Mode::Sched || md == Mode::SchedHpg)  // (variant 7's two: one unit with variant 7's scheduler)
+    return v == kSchedVariant ? Unit::SchedV7 : md == Mode::Sched ? Unit::Sched : Unit::SchedHpg;
   if (md == Mode::Bank || md == Mode::BankRec) return Unit::Bank;
   if (md == Mode::Hpg) return v == kSchedVariant ? Unit::HpgV7 : Unit::Hpg;
   return v == kSchedVariant ? Unit::V7 : Unit::Main;
@@ -134,9 +157,20 @@ template <Unit U, int V, Mode MD>
 inline void launch_cell(const Launch& l) {
   if constexpr (owner(V, MD) == U) {
     constexpr sfl::WaveShape w = sfl::kVariants[V];
-    constexpr bool TRACE = MD == Mode::Trace, TIMED = MD == Mode::Timed, HPG = MD == Mode::Hpg, EXT = MD == Mode::Ext;
+    constexpr bool TRACE = MD == Mode::Trace, TIMED = MD == Mode::Timed, HPG = MD == Mode::Hpg || MD == Mode::SchedHpg;
+    constexpr bool EXT = MD == Mode::Ext || MD == Mode::SchedExt;
+    constexpr bool SCHED = MD == Mode::Sched || MD == Mode::SchedHpg || MD == Mode::SchedExt;
     if (l.variant != V || l.mode != MD) return;
-    if constexpr (MD == Mode::Bank) {
+    if constexpr (SCHED) {
+      if constexpr (EXT && w.LM)
+        return;  // (no such cell: ext_variant maps the row to its twin)
+      else if constexpr (w.G < 64)
+        k_wave_g_sched<w.PPL, w.SPL, w.TW, w.G, w.OCC, (bool)w.LM, HPG, EXT><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
+      else if constexpr (two_slot(w))
+        k_wave2_sched<w.PPL, w.SPL, w.TW, HPG, EXT><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
+      else
+        k_wave_sched<w.PPL, w.SPL, w.TW, HPG, EXT><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
+    } else if constexpr (MD == Mode::Bank) {
       if constexpr (w.G < 64)
         k_wave_g_bank<w.PPL, w.SPL, w.TW, w.G, w.OCC, (bool)w.LM><<<grid_of(w, l.E), block_of(w), 0, l.stream>>>(l.m, l.s, l.c);
       else if constexpr (two_slot(w))
@@ -164,7 +198,8 @@ template <Unit U, int... I>
 inline void launch_owned(const Launch& l, std::integer_sequence<int, I...>) {
   ((launch_cell<U, I + 1, Mode::Plain>(l), launch_cell<U, I + 1, Mode::Trace>(l), launch_cell<U, I + 1, Mode::Timed>(l),
     launch_cell<U, I + 1, Mode::Hpg>(l), launch_cell<U, I + 1, Mode::Ext>(l), launch_cell<U, I + 1, Mode::Bank>(l),
-    launch_cell<U, I + 1, Mode::BankRec>(l)), ...);
+    launch_cell<U, I + 1, Mode::BankRec>(l), launch_cell<U, I + 1, Mode::Sched>(l), launch_cell<U, I + 1, Mode::SchedHpg>(l),
+    launch_cell<U, I + 1, Mode::SchedExt>(l)), ...);
 }
 // a unit's launches: declared here, defined (SFL_KWAVE_UNIT) in the unit itself
 template <Unit U>
@@ -181,6 +216,14 @@ template <>
 void launch_unit<Unit::Ext>(const Launch& l);
 template <>
 void launch_unit<Unit::Bank>(const Launch& l);
+template <>
+void launch_unit<Unit::Sched>(const Launch& l);
+template <>
+void launch_unit<Unit::SchedHpg>(const Launch& l);
+template <>
+void launch_unit<Unit::SchedV7>(const Launch& l);
+template <>
+void launch_unit<Unit::SchedExt>(const Launch& l);
 #define SFL_KWAVE_UNIT(U)                                                                           \
   template <>                                                                                       \
   void sflk::launch_unit<sflk::Unit::U>(const sflk::Launch& l) {                                    \
@@ -195,6 +238,10 @@ inline void launch(const Launch& l) {
     case Unit::HpgV7: return launch_unit<Unit::HpgV7>(l);
     case Unit::Ext: return launch_unit<Unit::Ext>(l);
     case Unit::Bank: return launch_unit<Unit::Bank>(l);
+    case Unit::Sched: return launch_unit<Unit::Sched>(l);
+    case Unit::SchedHpg: return launch_unit<Unit::SchedHpg>(l);
+    case Unit::SchedV7: return launch_unit<Unit::SchedV7>(l);
+    case Unit::SchedExt: return launch_unit<Unit::SchedExt>(l);
   }
 }
 

@@ -150,4 +150,19 @@ SFL_FN uint64_t mf_draw(uint64_t seed, uint64_t tick, uint64_t handle) {
                0x632BE59BD9B4E019ull);
 }
 
+// seed schedules (include/sfl.h sfl_episode_seed): the seed of episode k of an env created on `base`
+SFL_FN uint64_t episode_seed(uint64_t base, uint64_t k) {
+  if (k == 0) return base;
+  return mix64(base * 0x9E3779B97F4A7C15ull + k * 0xD1B54A32D192ED03ull + 0x5EED5C4ED01E5EEDull);
+}
+constexpr uint64_t SEED_HELD_OUT_EPISODE = 0xFFFFFFFFFFFFFFFFull;
+constexpr uint32_t SEED_HELDOUT_EXPLOIT = 1u;
+// the seed of learning episode t (greedy: an exploit round or a test episode) under schedule (pool, flags)
+SFL_FN uint64_t sched_seed(uint64_t base, uint32_t pool, uint32_t flags, int32_t t, bool greedy) {
+  uint64_t k;
+  if (greedy) k = (flags & SEED_HELDOUT_EXPLOIT) ? SEED_HELD_OUT_EPISODE : 0ull;
+  else k = pool ? (uint64_t)((uint32_t)t % pool) : (uint64_t)(uint32_t)t;
+  return episode_seed(base, k);
+}
+
 }  // namespace sfl

@@ -316,9 +316,14 @@ struct LastMove<false, N> {};
 // words and the Q update of post (a greedy post writes the successor slot's reward only), the arrival bonus, and every
 // key-set insert (the bank is never written).  The env's policy index is a group-uniform register (an SGPR at G = 64,
 // where the table's base pointer is held instead): see qbase()
+// SCHED: a handle with a seed schedule (sfl_set_seed_schedule): the malfunction stream is keyed by the
+// running episode's seed, eseed, instead of s.seed[e].  The value is group-uniform (two SGPRs at G = 64, two VGPRs
+// below): loaded from SflState::ep_seed by load(), derived again at every reset (sched_reset) and written back by
+// store() with the rest of the env's scalars -- never passed through memory inside a launch
 template <int PPL, int SPL, int TWc, bool PART = false, int G = 64, bool LM = false, bool HPG = false, bool EXT = false,
-          bool BANK = false>
+          bool BANK = false, bool SCHED = false>
 struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
+  static_assert(!(SCHED && (PART || BANK)), "seed schedules: the learning and the external-action shapes only");
   static_assert(!(BANK && (PART || HPG || EXT)), "policy-bank evaluation: the plain shapes (and the LM one) only");
   static_assert(!(HPG && PART), "hyperparameter groups are not part of the partitioned local step");
   static_assert(!(EXT && (PART || HPG || LM)), "external-action mode: the plain shapes only");
@@ -406,6 +411,8 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
   uint32_t lerr;  // error bits seen by this lane (OR-reduced on store)
   uint32_t hgrp = 0;  // HPG: the env's hyperparameter group (G = 64: wave-uniform, in an SGPR), loaded by load()
   uint32_t pol = 0;   // BANK, G < 64: the bank table the env follows (group-uniform), loaded by load()
+  uint64_t eseed = 0; // SCHED: the running episode's seed (group-uniform), loaded by load()
+  int32_t ext_ep = 0; // SCHED and EXT: the env's episode index (SflState::ep_t), held by ext_run()
   // this env's blocks: Q-table, key-set bitmap, (switch, train) slots (env-major [T][S] here,
   // so one env's slots are contiguous and a flush over switches is one coalesced access)
   double* qb;
@@ -1044,6 +1051,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     }
     if constexpr (HPG) hgrp = U((uint32_t)ld(m.env_group, (size_t)e));
     if constexpr (BANK && G < 64) pol = U(ld(m.bank_policy, (size_t)e));
+    if constexpr (SCHED) eseed = U(ld(s.ep_seed, (size_t)e));
     now = U(ld(s.elapsed, e));
     flags = U(ld(s.eflags, e));
     epoch = U(ld(s.epoch, e));
@@ -1167,6 +1175,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
       st(s.ep_ticks, e, ep_ticks);
       st(s.step_ctr, e, (int64_t)step_ctr);
       st(s.dec_total, e, ld(s.dec_total, e) + (int64_t)n_dec);
+      if constexpr (SCHED) st(s.ep_seed, (size_t)e, eseed);
     }
     return err;
   }
@@ -1225,6 +1234,16 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     }
   }
 
+  // the seed the tick's malfunction draws are keyed by
+  __device__ __forceinline__ uint64_t tick_seed() const {
+    if constexpr (SCHED) return eseed;
+    else return s.seed[e];
+  }
+  // SCHED: the seed of the episode that the reset behind this call starts -- learning episode t, or a greedy round
+  __device__ __forceinline__ void sched_reset(int32_t t, bool greedy) {
+    eseed = sched_seed(U(ld(s.seed, (size_t)e)), m.seed_pool, m.seed_flags, t, greedy);
+  }
+
   // ---- episode reset (switch_env.py:93-158, _init_ports 507-568) --------------------------------
   __device__ __forceinline__ void reset() {
     now = 0;
@@ -1273,7 +1292,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     }
     pf_ok = false;
     const int32_t t = ++now;
-    const uint64_t seed = s.seed[e];
+    const uint64_t seed = tick_seed();
     // the trains' timetable rows (LDS)
     vec_t<int32_t, 4> tt0[TPL], tt1[TPL];
 #pragma unroll
@@ -2590,6 +2609,9 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     int32_t o_next = -1, o_step = -1, o_trunc = 0;
     bool applied = false, emitted = false;
     uint32_t ticks = 0;
+    // SCHED: ep_t counts the episodes the env has started since sfl_env_begin, minus one; no episode is greedy
+    // (a member, not a local of this function: an unused local alone changed the unscheduled kernels' code)
+    if constexpr (SCHED) ext_ep = U(ld(s.ep_t, (size_t)e));
     if (act == -2) {  // SFL_ACTION_RESET: the episode-end reset, where the env stands
       phase = PH_RESET;
       flags &= ~(F_EXT_OBS | F_INFLIGHT);
@@ -2598,6 +2620,10 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
     Dec d;
     while (true) {
       if (phase == PH_RESET) {
+        if constexpr (SCHED) {
+          ext_ep += 1;
+          sched_reset(ext_ep, false);
+        }
         reset();
         phase = PH_TICK;
       }
@@ -2651,6 +2677,7 @@ struct WEnv : LastMove<BANK, (TWc + G - 1) / G> {
       st(x.step_now, e, o_step);
       st(x.n_mf, e, n_mf);
       st(x.truncated, e, o_trunc);
+      if constexpr (SCHED) st(s.ep_t, (size_t)e, ext_ep);
       uint64_t w[2];
       if constexpr (TPL * G <= 64 || TWc <= 32) {
         w[0] = arr_mask;
@@ -2734,13 +2761,15 @@ struct PhaseTimer {
 // the env stops at its episode's end, where bank_end() writes its outputs
 // REC (BANK only): the instantiation an evaluation with a recording armed launches (SflCtl::rec_*); the one without
 // it carries none of the recording's code, so an evaluation with no recording armed runs what it ran before
+// SCHED: a handle with a seed schedule (WEnv SCHED): the episode's seed derived at PH_RESET, behind the greedy choice
 template <int PPL, int SPL, int TW, bool TRACE, bool PART = false, bool TIMED = false, bool HPG = false, bool EXT = false,
-          bool BANK = false, bool REC = false>
+          bool BANK = false, bool REC = false, bool SCHED = false>
 __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const SflPart* P = nullptr) {
   static_assert(!(EXT && (TRACE || TIMED)), "external-action mode: no trace, no phase timers");
   static_assert(!(BANK && (TRACE || TIMED)), "policy-bank evaluation: no trace, no phase timers");
   static_assert(BANK || !REC, "a recording is a policy-bank evaluation's");
-  using V = WEnv<PPL, SPL, TW, PART, 64, false, HPG, EXT, BANK>;
+  static_assert(!(SCHED && (TRACE || TIMED)), "seed schedules: no trace, no phase timers");
+  using V = WEnv<PPL, SPL, TW, PART, 64, false, HPG, EXT, BANK, SCHED>;
   // semaphores, counters, prefetch records, rng, timetable (PART: one record, timetable from the map)
   // (PART: the launch's initial records / counters in place of the timetable copy)
   constexpr int LDS_WORDS =
@@ -2787,6 +2816,7 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
         if (c.exploit_freq > 0 && (ep_t + 1) % c.exploit_freq == 0 && !(v.flags & F_EXPLOIT_DONE)) v.flags |= F_GREEDY;
         else v.flags &= ~F_GREEDY;
       }
+      if constexpr (SCHED) v.sched_reset(ep_t, (v.flags & F_GREEDY) != 0);
       if constexpr (TIMED) tm.lap(TM_OTHER);
       v.reset();
       if constexpr (TIMED) tm.lap(TM_RESET);
@@ -2908,12 +2938,13 @@ __device__ void run(const SflMap& m, const SflState& s, const SflCtl& c, const S
 // one post step and one decision.  The groups of a wave diverge (one ticks while another decides);
 // a batch loop as in run() would hold every group until the longest batch of the wave is done.
 template <int PPL, int SPL, int TW, bool TRACE, int G, bool TIMED = false, bool LM = false, bool HPG = false, bool EXT = false,
-          bool BANK = false, bool REC = false>
+          bool BANK = false, bool REC = false, bool SCHED = false>
 __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) {
   static_assert(!(EXT && (TRACE || TIMED)), "external-action mode: no trace, no phase timers");
   static_assert(!(BANK && (TRACE || TIMED)), "policy-bank evaluation: no trace, no phase timers");
   static_assert(BANK || !REC, "a recording is a policy-bank evaluation's");
-  using V = WEnv<PPL, SPL, TW, false, G, LM, HPG, EXT, BANK>;
+  static_assert(!(SCHED && (TRACE || TIMED)), "seed schedules: no trace, no phase timers");
+  using V = WEnv<PPL, SPL, TW, false, G, LM, HPG, EXT, BANK, SCHED>;
   // per env: semaphores, counters, prefetch records, rng; per block: the timetable rows and the
   // per-switch / per-port map records (the groups of a wave read different switches' records: LDS
   // reads instead of vector loads)
@@ -2986,6 +3017,7 @@ __device__ void run_groups(const SflMap& m, const SflState& s, const SflCtl& c) 
         else v.flags &= ~F_GREEDY;
       }
       if (target) break;
+      if constexpr (SCHED) v.sched_reset(ep_t, (v.flags & F_GREEDY) != 0);
       v.reset();
       phase = PH_TICK;
     }

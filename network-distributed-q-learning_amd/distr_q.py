@@ -33,7 +33,12 @@ class DistrQLearning:
     def __init__(self, env: ASyncSwitchEnv, gamma=1.0, epsilon=0.4, epsilon_decay_rate=0.0, lr=0.4,
                  lr_decay_rate=0.0, default_q=0.0, seed=450565, lib=None, seeds: Optional[Sequence[int]] = None,
                  hparam_groups: Optional[Sequence[dict]] = None, env_group: Optional[Sequence[int]] = None,
-                 outputs: Optional[Sequence[Tuple[str, Sequence[int]]]] = None):
+                 outputs: Optional[Sequence[Tuple[str, Sequence[int]]]] = None, seed_pool: int = 1,
+                 heldout_exploit: bool = False):
+        """``seed_pool`` / ``heldout_exploit``: the seed schedule (``runtime.Batch.set_seed_schedule``): learning episode
+        t runs on ``runtime.episode_seed(seed, t % seed_pool)`` (0: on ``episode_seed(seed, t)``), and the exploit
+        rounds and ``test`` on the held-out seed instead of ``seed``.  The defaults are the reference's: every episode
+        replays the malfunctions of ``seed``."""
         self.env = env
         self.gamma = gamma
         self.initial_epsilon = epsilon
@@ -59,7 +64,7 @@ class DistrQLearning:
         self.batch = runtime.Batch(env.compiled, self.hp, seeds, lib=lib, device=env.device, max_steps=env.max_steps,
                                    malfunction_stream=getattr(env, "malfunction_stream", "counter"),
                                    delay_threshold=getattr(env, "delay_threshold", 20), hparam_groups=hparam_groups,
-                                   env_group=env_group)
+                                   env_group=env_group, seed_pool=seed_pool, heldout_exploit=heldout_exploit)
 
     # ------------------------------------------------------------------
     @property
@@ -250,7 +255,9 @@ class DistrQLearning:
         greedy episode: its cum_reward must be the test's), one PNG per decision."""
         from . import render
         b = self.batch
-        ev = runtime.EvalBatch(b.cm, self.hp, [b.seeds[0]], 1, lib=b.lib, device=self.env.device,
+        # (a test episode runs on the base seed, or with held-out exploit rounds on the held-out one)
+        seed = runtime.episode_seed(b.seeds[0], runtime.HELD_OUT_EPISODE) if b.seed_schedule()[1] else b.seeds[0]
+        ev = runtime.EvalBatch(b.cm, self.hp, [seed], 1, lib=b.lib, device=self.env.device,
                                max_steps=self.env.max_steps, malfunction_stream=b.malfunction_stream,
                                delay_threshold=getattr(self.env, "delay_threshold", 20))
         try:

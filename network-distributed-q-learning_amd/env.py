@@ -44,14 +44,17 @@ class ASyncSwitchEnv:
     observer.py).  ``malfunction_stream="flatland"`` draws malfunctions in the order of Flatland's
     ``ParamMalfunctionGen`` on the reset-seeded ``np_random`` (mfstream.py) instead of the
     counter-based stream of the frozen spec.  ``env_kernel``: the AEC protocol's env step, ``"lane"``, ``"wave"`` or
-    None (``SFL_ENV_KERNEL``, default ``"lane"``): ``aec.AECBatch``'s ``kernel``.
+    None (``SFL_ENV_KERNEL``, default ``"lane"``): ``aec.AECBatch``'s ``kernel``.  ``seed_pool``: ``aec.AECBatch``'s
+    seed schedule -- the n-th ``reset()`` on one seed runs on ``runtime.episode_seed(seed, n % seed_pool)`` (0: on
+    ``episode_seed(seed, n)``) instead of replaying the same malfunctions; the device env is kept across them.
     """
 
     def __init__(self, rail_env: Union[str, "mapgen.Scenario"], max_steps: int = 200, render_mode=None,
                  observer=None, seed: Optional[int] = None, n_envs: int = 1, device: int = 0,
-                 malfunction_stream: str = "counter", env_kernel: Optional[str] = None):
+                 malfunction_stream: str = "counter", env_kernel: Optional[str] = None, seed_pool: int = 1):
         self.observer = observer
         self.env_kernel = env_kernel
+        self.seed_pool = int(seed_pool)
         self.delay_threshold = observer_mod.delay_threshold_of(observer)
         if isinstance(rail_env, str):
             sc = mapgen.make_config(rail_env) if rail_env in mapgen.CONFIGS else mapgen.Scenario.load(rail_env)
@@ -98,7 +101,7 @@ class ASyncSwitchEnv:
                 aec.close()
             self._aec = AECBatch(self.compiled, [seed], lib=lib, device=self.device, max_steps=self.max_steps,
                                  malfunction_stream=self.malfunction_stream, delay_threshold=self.delay_threshold,
-                                 kernel=self.env_kernel)
+                                 kernel=self.env_kernel, seed_pool=self.seed_pool)
             self._aec_seed = seed
             out = self._aec.step(None)
         else:

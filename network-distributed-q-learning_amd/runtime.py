@@ -29,6 +29,26 @@ def numpy_rng_state(seed: int) -> List[int]:
     return [s >> 64, s & m, inc >> 64, inc & m, (int(st["has_uint32"]) << 32) | int(st["uinteger"])]
 
 
+HELD_OUT_EPISODE = _lib.SEED_HELD_OUT_EPISODE
+_M64 = (1 << 64) - 1
+
+
+def _mix64(z: int) -> int:
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def episode_seed(base: int, k: int) -> int:
+    """The seed episode ``k`` of an env created on ``base`` runs on under a seed schedule (include/sfl.h
+    sfl_episode_seed): ``base`` itself for k == 0; ``HELD_OUT_EPISODE`` is the index of the held-out exploit rounds.
+    Also how an ``EvalBatch`` is given a table's training pool: ``[episode_seed(base, k) for k in range(pool)]``."""
+    base, k = int(base) & _M64, int(k) & _M64
+    if k == 0:
+        return base
+    return _mix64((base * 0x9E3779B97F4A7C15 + k * 0xD1B54A32D192ED03 + 0x5EED5C4ED01E5EED) & _M64)
+
+
 def raw_to_dict(cm: CompiledMap, default_q: float, q: np.ndarray, touched: np.ndarray) -> Dict[tuple, list]:
     """A compact Q block and key-set bitmap (the layout of Batch.q_raw) as the reference's ``q_table`` dict:
     touched rows as {observation tuple: [Q per action]}."""
@@ -110,16 +130,18 @@ class BatchState:
     ``state`` [n][state_bytes] uint8 (one record per env: episode state, RNG, interaction counts, pending-update
     slots, seed), ``touched`` [n][touched_words] uint32 (the key sets), ``row_off`` / ``cell_off`` [n + 1] uint64,
     ``row_ids`` uint32 (each env's live Q rows, ascending) and ``cells`` uint64 (their cells as bit patterns);
-    ``seeds`` [n] uint64; ``sched`` [n][4] float64, the (epsilon, epsilon_decay_rate, lr, lr_decay_rate) each env
-    learns with; ``fingerprint`` (of the map, gamma, default_q, ntab, max_steps, delay_threshold, the malfunction
+    ``seeds`` [n] uint64 (the base seeds); ``sched`` [n][4] float64, the (epsilon, epsilon_decay_rate, lr,
+    lr_decay_rate) each env learns with; ``seed_schedule`` the (pool, flags) of the batch's seed schedule ((1, 0), and
+    absent from a saved file, for a batch that never left the default); ``fingerprint`` (of the map, gamma, default_q, ntab, max_steps, delay_threshold, the malfunction
     stream's kind and the layout class) and ``layout`` ("lane" or "wave": which kernels' record format)."""
 
     ARRAYS = (("state", np.uint8), ("touched", np.uint32), ("row_off", np.uint64), ("row_ids", np.uint32),
               ("cell_off", np.uint64), ("cells", np.uint64), ("seeds", np.uint64), ("sched", np.float64))
 
-    def __init__(self, fingerprint: int, layout: str, **arrays):
+    def __init__(self, fingerprint: int, layout: str, seed_schedule=(1, 0), **arrays):
         self.fingerprint = int(fingerprint)
         self.layout = str(layout)
+        self.seed_schedule = (int(seed_schedule[0]), int(seed_schedule[1]))
         for name, dt in self.ARRAYS:
             setattr(self, name, np.ascontiguousarray(arrays[name], dt))
 
@@ -128,15 +150,17 @@ class BatchState:
 
     def save(self, path) -> None:
         """One uncompressed .npz written to exactly ``path``."""
+        extra = {} if self.seed_schedule == (1, 0) else {"seed_schedule": np.array(self.seed_schedule, np.uint32)}
         with open(path, "wb") as f:
             np.savez(f, fingerprint=np.array([self.fingerprint], np.uint64),
                      layout=np.array([_lib.STATE_LAYOUTS.index(self.layout)], np.uint32),
-                     **{name: getattr(self, name) for name, _ in self.ARRAYS})
+                     **{name: getattr(self, name) for name, _ in self.ARRAYS}, **extra)
 
     @classmethod
     def load(cls, path) -> "BatchState":
         with np.load(path, allow_pickle=False) as z:
-            return cls(int(z["fingerprint"][0]), _lib.STATE_LAYOUTS[int(z["layout"][0])],
+            sched = tuple(int(v) for v in z["seed_schedule"]) if "seed_schedule" in z.files else (1, 0)
+            return cls(int(z["fingerprint"][0]), _lib.STATE_LAYOUTS[int(z["layout"][0])], seed_schedule=sched,
                        **{name: z[name] for name, _ in cls.ARRAYS})
 
 
@@ -242,8 +266,10 @@ class Batch:
     def __init__(self, cm: CompiledMap, hp: dict, seeds: Sequence[int], lib: Optional[_lib.Lib] = None,
                  device: int = 0, max_steps: int = 100_000, ntab: int = NTAB, malfunction_stream: str = "counter",
                  delay_threshold: int = 20, hparam_groups: Optional[Sequence[dict]] = None,
-                 env_group: Optional[Sequence[int]] = None):
-        """``hparam_groups`` / ``env_group``: hyperparameter groups (``set_hparam_groups``) -- env e learns with the
+                 env_group: Optional[Sequence[int]] = None, seed_pool: int = 1, heldout_exploit: bool = False):
+        """``seed_pool`` / ``heldout_exploit``: the seed schedule (``set_seed_schedule``); the defaults replay one
+        malfunction realisation per env, as the reference does.
+        ``hparam_groups`` / ``env_group``: hyperparameter groups (``set_hparam_groups``) -- env e learns with the
         ``epsilon``, ``epsilon_decay_rate``, ``lr`` and ``lr_decay_rate`` of ``hparam_groups[env_group[e]]``; ``hp``
         still gives ``gamma`` and ``default_q`` (and the schedule of an ungrouped batch).
         ``malfunction_stream``: "counter" (the counter-based draw of the frozen Flatland spec,
@@ -274,6 +300,12 @@ class Batch:
         if hparam_groups is not None or env_group is not None:
             try:
                 self.set_hparam_groups(hparam_groups, env_group)
+            except Exception:
+                self.close()
+                raise
+        if int(seed_pool) != 1 or heldout_exploit:
+            try:
+                self.set_seed_schedule(seed_pool, heldout_exploit)
             except Exception:
                 self.close()
                 raise
@@ -332,6 +364,36 @@ class Batch:
         self.lib.check(self.lib.dll.sfl_set_hparam_groups(self.h, len(groups), arr, _ptr(ega, C.c_uint16)),
                        "sfl_set_hparam_groups")
         self.hparam_groups, self.env_group = groups, eg
+
+    # ---- seed schedules (sfl_set_seed_schedule): a fresh malfunction stream per episode ----
+    def set_seed_schedule(self, pool: int, heldout_exploit: bool = False) -> None:
+        """From each env's next reset on, learning episode t of env e (its index since ``learn_begin``; in
+        external-action mode the episodes started since begin, minus one) runs on ``episode_seed(seeds[e], t % pool)``
+        -- ``pool`` 0: on ``episode_seed(seeds[e], t)``, every episode new -- and a greedy episode (an exploit round,
+        ``test``) on ``seeds[e]``, or with ``heldout_exploit`` on ``episode_seed(seeds[e], HELD_OUT_EPISODE)``, which no
+        learning episode uses.  ``pool`` 1 without ``heldout_exploit`` is the default.  ``self.seeds`` stay the base
+        seeds.  The library refuses (``SflError``) what include/sfl.h lists."""
+        pool = int(pool)
+        if pool < 0 or pool > 0xFFFFFFFF:
+            raise ValueError(f"set_seed_schedule: pool {pool} is not a 32-bit count")
+        flags = _lib.SEED_HELDOUT_EXPLOIT if heldout_exploit else 0
+        self.lib.check(self.lib.dll.sfl_set_seed_schedule(self.h, pool, flags), "sfl_set_seed_schedule")
+
+    def seed_schedule(self) -> Tuple[int, bool]:
+        """(pool, heldout_exploit) as the handle holds them."""
+        pool, flags = C.c_uint32(0), C.c_uint32(0)
+        self.lib.check(self.lib.dll.sfl_get_seed_schedule(self.h, C.byref(pool), C.byref(flags)), "sfl_get_seed_schedule")
+        return int(pool.value), bool(flags.value & _lib.SEED_HELDOUT_EXPLOIT)
+
+    def _seed_schedule_raw(self) -> Tuple[int, int]:
+        pool, held = self.seed_schedule()
+        return pool, (_lib.SEED_HELDOUT_EXPLOIT if held else 0)
+
+    def episode_seeds(self) -> np.ndarray:
+        """[E] uint64: the seed of the episode each env started last (its base seed before its first reset)."""
+        out = np.zeros(self.E, np.uint64)
+        self.lib.check(self.lib.dll.sfl_get_episode_seeds(self.h, _ptr(out, C.c_uint64)), "sfl_get_episode_seeds")
+        return out
 
     def _qinit_arrays(self):
         cm = self.cm
@@ -665,7 +727,7 @@ class Batch:
         so = info["seed_offset"]
         seeds = np.ascontiguousarray(state[:, so: so + 8]).view(np.uint64).reshape(-1)
         sched = np.array([self._sched(int(e)) for e in ids], np.float64).reshape(len(ids), 4)
-        return BatchState(info["fingerprint"], info["layout"], state=state, touched=touched, row_off=row_off,
+        return BatchState(info["fingerprint"], info["layout"], seed_schedule=self._seed_schedule_raw(), state=state, touched=touched, row_off=row_off,
                           row_ids=row_ids, cell_off=cell_off, cells=cells, seeds=seeds, sched=sched)
 
     def restore(self, state: BatchState, into: Optional[Sequence[int]] = None) -> None:
@@ -674,7 +736,8 @@ class Batch:
         counts and seed the record's; ``self.seeds`` follows, and with ``malfunction_stream="flatland"`` the schedule is
         expanded again for the new seeds and uploaded.  No other env changes.  Raises ``ValueError`` when a slot's
         four schedule values (its group's, or ``hp``'s) differ bitwise from the ones the env was captured with -- the
-        record's interaction counts index those tables, so continuing on other schedules is not a resume -- and
+        record's interaction counts index those tables, so continuing on other schedules is not a resume --, or when
+        the batch's seed schedule is not the one the records were captured under, and
         ``SflError`` for what the library refuses (another map, gamma, default_q, ntab, max_steps, delay_threshold,
         malfunction stream or layout class; a slot out of range or listed twice; inconsistent arrays), leaving the
         batch unchanged.  A running curve does not carry over: call ``curve_begin`` after ``restore``."""
@@ -682,6 +745,10 @@ class Batch:
         slots = self._env_list(range(n) if into is None else into, "restore")
         if len(slots) != n:
             raise ValueError(f"restore: {len(slots)} slots for {n} records")
+        if n and tuple(state.seed_schedule) != self._seed_schedule_raw():
+            raise ValueError(f"restore: the batch's seed schedule (pool, flags) = {self._seed_schedule_raw()}, the "
+                             f"records were captured under {tuple(state.seed_schedule)}: the running episodes' seeds "
+                             "follow from the schedule, so continuing on another one is not a resume")
         for k, e in enumerate(slots):
             if int(e) < self.E:
                 mine = np.array(self._sched(int(e)), np.float64)

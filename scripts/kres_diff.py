@@ -5,7 +5,8 @@ compares against one from before it; HPG = true kernels are listed on their own.
 (external-action mode's kernels, sfl_env_begin_wave).  The policy-bank evaluation's kernels (k_wave_bank, k_wave2_bank,
 k_wave_g_bank: sfl_bank_eval) are listed as "BANK " + the key of their Plain twin (those of an evaluation with a
 recording armed, k_wave*_bank_rec, as "BANKREC " + that key), and a second table puts each beside
-that twin.  The "code" column says whether the
+that twin.  The kernels of handles with a seed schedule (k_wave_sched, k_wave2_sched, k_wave_g_sched) are listed as
+"SCHED " + the key of their unscheduled twin (Plain, HPG or EXT), with a table of their own beside those twins.  The "code" column says whether the
 kernel's machine code (the symbol's bytes in its code object's .text) is the same in both, or the same but for
 pc-relative addresses (same_code).  Exit status 1 if a kernel
 present in both differs in a resource field (registers, spills, scratch, LDS); code bytes alone do not fail.  The
@@ -67,7 +68,7 @@ def kernels_of(co):
     for blk in notes.split("- .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", blk).group(1)
         # (Itanium mangling: k_waveILi8ELi2ELb1E...E -- integer and bool template arguments only)
-        m = re.search(r"\d+(k_wave_g_bank_rec|k_wave2_bank_rec|k_wave_bank_rec|k_wave_g_bank|k_wave2_bank|k_wave_bank|k_wave_g|k_wave2_part|k_wave_part|k_wave2|k_wave)I((?:L[ib]\d+E)+)E", name)
+        m = re.search(r"\d+(k_wave_g_sched|k_wave2_sched|k_wave_sched|k_wave_g_bank_rec|k_wave2_bank_rec|k_wave_bank_rec|k_wave_g_bank|k_wave2_bank|k_wave_bank|k_wave_g|k_wave2_part|k_wave_part|k_wave2|k_wave)I((?:L[ib]\d+E)+)E", name)
         if not m:
             # the transition assembler's kernels (sfl_trans.hip) and the cell folds with their reset kernels
             # (sfl_curve.hip, sfl_eval.hip): no template arguments, listed by name
@@ -82,6 +83,12 @@ def kernels_of(co):
             twin = args[:3] + ["false"] + (args[3:5] + ["false", args[5]] if len(args) == 6 else ["false"])
             rec = m.group(1).endswith("_rec")  # (the kernels of an evaluation with a recording armed: listed on their own)
             out[("BANKREC " if rec else "BANK ") + m.group(1)[:-9 if rec else -5] + "<" + ",".join(twin) + ">"] = \
+                vals + [size.get(name, -1), code.get(name)]
+            continue
+        if m.group(1).endswith("_sched"):  # <PPL,SPL,TW[,G,OCC,LM],HPG,EXT>: "SCHED " + the key of the unscheduled twin
+            base, (hpg, ext) = m.group(1)[:-6], (v == "true" for v in args[-2:])
+            twin = args[:3] + ["false"] + (args[3:5] + ["false", args[5]] if len(args) == 8 else ["false"])
+            out["SCHED " + ("EXT " if ext else "") + ("HPG " if hpg else "") + base + "<" + ",".join(twin) + ">"] = \
                 vals + [size.get(name, -1), code.get(name)]
             continue
         full = {"k_wave": 6, "k_wave2": 6, "k_wave_g": 9}.get(m.group(1))  # (the part kernels have no HPG argument)
@@ -142,6 +149,18 @@ def main(old, new, md=False):
         print("\npolicy-bank kernels of the new library beside their Plain twins (twin -> bank)")
         bh = ["kernel"] + head[1:8]
         brows = [[k[5:]] + [f"{x} -> {y}" for x, y in zip(b[k[5:]][:-1], b[k][:-1])] for k in banks]
+        if md:
+            print("| " + " | ".join(bh) + " |\n|" + "---|" * len(bh))
+            for r in brows:
+                print("| " + " | ".join(r) + " |")
+        else:
+            for r in [bh] + brows:
+                print(f"{r[0]:64s}" + "".join(f"{x:>24s}" for x in r[1:]))
+    scheds = [k for k in sorted(b) if k.startswith("SCHED ") and k[6:] in b]
+    if scheds:
+        print("\nseed-schedule kernels of the new library beside their unscheduled twins (twin -> scheduled)")
+        bh = ["kernel"] + head[1:8]
+        brows = [[k[6:]] + [f"{x} -> {y}" for x, y in zip(b[k[6:]][:-1], b[k][:-1])] for k in scheds]
         if md:
             print("| " + " | ".join(bh) + " |\n|" + "---|" * len(bh))
             for r in brows:
